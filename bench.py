@@ -11,11 +11,21 @@ Launch: `torchrun --nproc-per-node N bench.py --gpus N` (RANK / LOCAL_RANK / WOR
 environment), or `python bench.py --gpus N`, which starts the N rank processes itself before
 anything touches the GPU.
 
-Printed (rank 0, one JSON line): value = lookupN(3)/s over all ranks, the dominant kernel's
-roofline (48 algorithmic bytes per lookupN(3): 36 B key read + 12 B owner write),
-the CPU oracle timed on this host as cpu_baseline, and the other configs' legs: C3 merge
-(+ fold roofline, CPU baselines), C4 and C5 gossip simulations (+ traffic, per-round spread,
-CPU baselines), the wire codec.
+Printed (rank 0, one JSON line): value = lookupN(3)/s over all ranks, ms_per_step, and the
+dominant kernel's roofline (48 algorithmic bytes per lookupN(3): 36 B key read + 12 B owner
+write) from the same timed steps. A plain run does no more than that: set up, warm
+up, time --steps steps, print.
+
+--dump-outputs DIR writes what the last timed step computed to DIR/owners.npy (rank r > 0:
+owners_rank<r>.npy): the owners of a fixed, seeded sample of that step's keys (the first and last
+4096 keys and 2^20 drawn ones), float64 [sample, nrep], with the sampled key indices in
+owners_index.npy. The keys are a function of the arguments alone, so two builds can be compared
+output for output.
+
+--full adds the legs that take runs of their own: the CPU oracle timed on this host as
+cpu_baseline, and the other configs' legs: C3 merge (+ fold roofline, CPU baselines), C4 and C5
+gossip simulations (+ traffic, per-round spread, CPU baselines), the wire codec, the Node
+per-call latencies. The --no-* / --sim*-n options select among them.
 """
 import argparse
 import json
@@ -588,6 +598,32 @@ def pmc_traffic(keys, servers, nrep):
     return per_key * keys, src
 
 
+DUMP_EDGE = 4096  # keys kept from each end of the batch (the first and the last tiles)
+DUMP_DRAWN = 1 << 20  # keys drawn in between (seeded): 3 x 8 B x ~2^20 = 25 MB at nrep 3
+
+
+def dump_sample_index(n):
+    """The key indices --dump-outputs keeps of an n-key step: all of them up to 2^20 + 8192 keys,
+    else both ends and 2^20 drawn with a fixed seed (sorted; a repeat is harmless)."""
+    if n <= DUMP_DRAWN + 2 * DUMP_EDGE:
+        return np.arange(n, dtype=np.int64)
+    drawn = np.random.default_rng(20260).integers(DUMP_EDGE, n - DUMP_EDGE, size=DUMP_DRAWN, dtype=np.int64)
+    return np.concatenate([np.arange(DUMP_EDGE, dtype=np.int64), np.sort(drawn),
+                           np.arange(n - DUMP_EDGE, n, dtype=np.int64)])
+
+
+def dump_outputs(torch, path, owners, n, nrep, rank):
+    """--dump-outputs: the owners array the last timed step wrote (what a caller of lookupn_dev
+    receives), sampled by dump_sample_index, as float64 (owner ids are u32: exact)."""
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample_index(n)
+    rows = owners.view(n, nrep)[torch.from_numpy(idx).cuda()].cpu().numpy().view(np.uint32)
+    suffix = "_rank%d" % rank if rank else ""
+    np.save(os.path.join(path, "owners%s.npy" % suffix), rows.astype(np.float64))
+    if rank == 0:
+        np.save(os.path.join(path, "owners_index.npy"), idx.astype(np.float64))
+
+
 # ------------------------------------------------------------------ launcher
 
 def _free_port():
@@ -630,6 +666,11 @@ def main():
                     help="after the W warmup steps, keep stepping (untimed) until this much warm-up time has "
                          "passed: the lookup kernel speeds up over its first ~15 launches (1.19 -> 0.90 ms) "
                          "while the device clocks ramp")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: CPU baselines, C3 merge, C4/C5 "
+                         "simulations, wire codec, Node per-call latency (chosen among by the --no-* options)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's owners (a fixed seeded sample, float64) to DIR/owners.npy")
     ap.add_argument("--batch-log2", type=int, default=26)
     ap.add_argument("--servers", type=int, default=10000)
     ap.add_argument("--nrep", type=int, default=3)
@@ -724,14 +765,16 @@ def main():
     elapsed, kern_ms = reduce_max([elapsed, kern_ms])
 
     total = B * args.steps * world
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, owners, B, args.nrep, rank)
     del keys, owners
     torch.cuda.empty_cache()
     merge = None
-    if not args.no_merge:
+    if args.full and not args.no_merge:
         merge = merge_bench(rpa, torch, local, batches=args.merge_batches, world=world, dist=dist,
                             reduce_max=reduce_max, part_log2=args.part_log2)
     sim5 = sim_bench(rpa, torch, dist, local, n=args.sim5_n, world=world, reduce_max=reduce_max) \
-        if args.sim5_n else None
+        if args.full and args.sim5_n else None
     if rank == 0:
         achieved = BYTES_PER_LOOKUPN3 * B / (kern_ms * 1e-3) / 1e9
         traffic, traffic_src = pmc_traffic(B, args.servers, args.nrep)
@@ -766,15 +809,15 @@ def main():
             out["merge"] = merge
             if not args.no_cpu and world == 1:
                 out["merge"]["cpu_baseline"] = merge_cpu_baseline(100_000, 100_000, th)
-        if args.sim_n and world == 1:
+        if args.full and args.sim_n and world == 1:
             out["sim"] = sim_bench(rpa, torch, dist, local, n=args.sim_n)
         if sim5:
             out["sim_c5"] = sim5
-        if not args.no_wire:
+        if args.full and not args.no_wire:
             out["wire"] = wire_bench(rpa, torch, local)
-        if not args.no_api and world == 1:
+        if args.full and not args.no_api and world == 1:
             out["api_latency"] = api_latency_bench()
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(servers, args.cpu_keys, th)
             if args.sim_n and "sim" in out:
                 out["sim"]["cpu_baseline"] = sim_cpu_baseline(args.sim_n, threads=th)

@@ -26,7 +26,7 @@ def _bench(gpus, extra, env_extra=None):
     return json.loads(lines[0])
 
 
-SMALL = ["--steps", "2", "--warmup", "1", "--batch-log2", "18", "--no-merge", "--no-wire", "--no-cpu",
+SMALL = ["--full", "--steps", "2", "--warmup", "1", "--batch-log2", "18", "--no-merge", "--no-wire", "--no-cpu",
          "--sim-n", "0", "--sim5-n", "3000"]
 
 
@@ -65,3 +65,52 @@ def test_bench_four_ranks_spawned_with_merge(gpu):
     # the exchange's host and device time per round, shown with -rP
     print("sim_c5 exchange:", json.dumps({k: v for k, v in out["sim_c5"].items()
                                           if k.startswith("exchange") or k in ("rounds", "round_ms")}))
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(gpu, orc, tmp_path):
+    """Without --full the line holds the headline figure alone (no leg beside the timed steps),
+    --steps sets the timed steps, and --dump-outputs writes the last timed step's owners: with
+    --steps 3 that step read key buffer 2 (keys 2 * 2^18 ...), checked here against the oracle
+    by server name."""
+    import numpy as np
+
+    n, servers = 1 << 18, 500
+    out = _bench(1, ["--steps", "3", "--warmup", "1", "--batch-log2", "18", "--servers", str(servers),
+                     "--dump-outputs", str(tmp_path / "dump")])
+    assert out["steps"] == 3 and out["config"]["total_keys"] == 3 * n
+    assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(n / (out["ms_per_step"] * 1e-3))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in out
+    for k in ("merge", "sim", "sim_c5", "wire", "api_latency", "cpu_baseline"):
+        assert k not in out
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["owners.npy", "owners_index.npy"]
+    got = np.load(tmp_path / "dump" / "owners.npy")
+    idx = np.load(tmp_path / "dump" / "owners_index.npy")
+    assert got.dtype == np.float64 and got.shape == (n, 3)
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.arange(n))
+    names = [orc.c2_addr(i) for i in range(servers)]
+    ring = gpu.HashRing(device=0)
+    ring.addRemoveServers(names)
+    oracle = orc.Ring(100)
+    oracle.add_remove(names)
+    want, _ = oracle.lookupn_keys(orc.uuid_keys(42, 2 * n, n), 3)
+    gname = np.array([ring.name(i) for i in range(servers)])
+    wname = np.array([oracle.name(i) for i in range(servers)])
+    assert np.array_equal(gname[got.astype(np.int64)], wname[np.asarray(want).astype(np.int64)])
+
+
+def test_bench_dump_sample_is_fixed():
+    """The sample --dump-outputs keeps of a full-size step: both ends, 2^20 drawn keys, the same
+    on every call, under 64 MB as float64 owners plus indices."""
+    import importlib.util
+
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("rp_bench", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = 1 << 26
+    a, b = bench.dump_sample_index(n), bench.dump_sample_index(n)
+    assert np.array_equal(a, b) and a[0] == 0 and a[-1] == n - 1 and a.min() >= 0 and a.max() < n
+    assert np.array_equal(a[:4096], np.arange(4096)) and np.all(np.diff(a) >= 0)
+    assert len(a) * (3 + 1) * 8 <= 64 << 20
+    assert np.array_equal(bench.dump_sample_index(1000), np.arange(1000))

@@ -6,10 +6,10 @@ TAG=${1:-r02}
 shift || true
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
-timeout -k 10 600 python3 -u bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench rc=$?"; tail -5 "$OUT/bench.err"; exit 1; }
+timeout -k 10 600 python3 -u bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench rc=$?"; tail -5 "$OUT/bench.err"; exit 1; }
 echo "bench ok"
 export TMPDIR=/tmp
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 -u bench.py --no-cpu "$@" \
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 -u bench.py --full --no-cpu "$@" \
     > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || { echo "rocprof rc=$?"; tail -5 "$OUT/prof.err"; exit 1; }
 echo "rocprof ok"
 find "$OUT/prof" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;

@@ -18,7 +18,7 @@ for v in ${2:-auto hw0}; do
     cu6) export RP_SIM_PC32_PER_CU=6 ;;
     *) export RP_SIM_CK=$v RP_SIM_TWINS=1 ;;
   esac
-  timeout -k 10 240 python3 -u bench.py --no-cpu --no-merge --no-wire \
+  timeout -k 10 240 python3 -u bench.py --full --no-cpu --no-merge --no-wire \
       --batch-log2 20 --steps 2 --warmup 1 > "$OUT/$v.json" 2> "$OUT/$v.err" || { echo "$v rc=$?"; tail -3 "$OUT/$v.err"; exit 1; }
   python3 - "$OUT/$v.json" "$v" <<'PY'
 import json, sys

@@ -6,7 +6,7 @@ TAG=${1:-mab}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
 for v in ${2:-64 128}; do
-  RP_MEMBERS_GROUP_SLOTS=$v timeout -k 10 240 python3 -u bench.py --no-cpu --no-wire --sim-n 0 --sim5-n 0 \
+  RP_MEMBERS_GROUP_SLOTS=$v timeout -k 10 240 python3 -u bench.py --full --no-cpu --no-wire --sim-n 0 --sim5-n 0 \
       --batch-log2 20 --steps 2 --warmup 1 > "$OUT/$v.json" 2> "$OUT/$v.err" || { echo "$v rc=$?"; tail -3 "$OUT/$v.err"; exit 1; }
   python3 - "$OUT/$v.json" "$v" <<'PY'
 import json, sys

@@ -9,7 +9,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY 
            "SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_BRANCH SQ_ACTIVE_INST_SCA"; do
   tag=$(echo $grp | cut -d' ' -f1-2 | tr ' ' '_')
   timeout -s KILL 150 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d "$OUT/$tag" -o run -- \
-      python3 bench.py --no-cpu --no-api --sim-n 0 --sim5-n 0 --no-merge --steps 1 --warmup 0 --batch-log2 20 > "$OUT/$tag.log" 2>&1
+      python3 bench.py --full --no-cpu --no-api --sim-n 0 --sim5-n 0 --no-merge --steps 1 --warmup 0 --batch-log2 20 > "$OUT/$tag.log" 2>&1
   rc=$?
   echo "pmc $tag rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$OUT/$tag.log"; exit $rc; fi

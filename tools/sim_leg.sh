@@ -10,7 +10,7 @@ timeout -k 10 600 python3 -u -m pytest tests/test_sim_gpu.py tests/test_sim_shar
 rc=$?; tail -2 "$OUT/test.log"; [ $rc -eq 0 ] || exit $rc
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 -u bench.py \
-    --no-cpu --no-merge --no-wire --steps 2 --warmup 1 > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench rc=$?"; tail -5 "$OUT/bench.err"; exit 1; }
+    --full --no-cpu --no-merge --no-wire --steps 2 --warmup 1 > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench rc=$?"; tail -5 "$OUT/bench.err"; exit 1; }
 find "$OUT/prof" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
 python3 - "$OUT" <<'PY'
 import json, sys
