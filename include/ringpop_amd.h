@@ -152,6 +152,51 @@ int rp_ring_group_keys(rp_ring *r, const char *keys, const uint64_t *off, uint32
 int rp_ring_group_hashes(rp_ring *r, const uint32_t *hashes, uint64_t n, uint32_t self_id, uint32_t *dests,
                          uint32_t *group_off, uint32_t *perm, uint32_t *ndest);
 
+/* Ring snapshots: an immutable device copy of the ring's exact lookup arrays (sorted tokens,
+ * owners, bucket index) as of the call, with the token count, server count and checksum of that
+ * moment. A snapshot owns its memory and holds no pointer into the ring: it stays valid across
+ * any number of later rp_ring_add_remove calls and may be destroyed before or after the ring.
+ * Its owner ids are the ring's interned ids (stable for the life of the ring; resolve names with
+ * rp_ring_owner_name on the ring). A snapshot of an empty ring is legal. rp_ring_snapshot is a
+ * device call on r (it stops a resident service and is ordered after pending rebuilds). */
+typedef struct rp_ring_snap rp_ring_snap;
+int rp_ring_snapshot(rp_ring *r, rp_ring_snap **out);
+int rp_ring_snap_destroy(rp_ring_snap *s);
+int rp_ring_snap_info(const rp_ring_snap *s, uint32_t *token_count, uint32_t *server_count,
+                      uint32_t *checksum, int *checksum_is_set);
+/* lookupN under the snapshotted ring: the rows rp_ring_lookupn_dev wrote at snapshot time
+ * (answering under the old ring, e.g. the request proxy's checksum-mismatch case). */
+int rp_ring_snap_lookupn_dev(rp_ring_snap *s, const uint8_t *d_keys, const uint64_t *d_off, uint32_t stride,
+                             uint64_t n, int32_t nrep, uint32_t *d_owners, uint8_t *d_counts, void *stream);
+
+/* Moved keys: which keys changed hands between a snapshot and the ring now (hand-off after
+ * ringChanged). Key i has moved iff its lookupN(key, nrep) row under `before` differs from its
+ * row under r, compared as ordered lists including their lengths; rows have W = max(nrep, 1)
+ * slots padded with RP_NULL_ID, exactly what rp_ring_lookupn* writes (nrep <= 0 keeps lookupn's
+ * single-step form). One pass: each key is read and hashed once, both rings are searched from
+ * that hash, and rows are written for moved keys only.
+ *   *count                    the number of moved keys, counted in full
+ *   idx[0 .. min(count,cap))  the moved key indices, ascending (input order)
+ *   before_rows / after_rows  [j*W .. j*W+W): the two rows of key idx[j]; either may be NULL
+ * Nothing at or past entry cap is touched (cap = 0: count only; idx may then be NULL).
+ * `before` must be a snapshot of a ring on r's device with r's id space (normally of r itself).
+ * nrep > 8 and n >= 2^32 return RP_EINVAL (rows are compared in registers, 8 owners at most).
+ * The _dev form takes device buffers (d_count one uint32), is stream-ordered and never syncs
+ * with the host, except that a stream other than the ring's own first waits for the ring's
+ * pending rebuilds (as rp_ring_lookupn_dev does). */
+int rp_ring_moved_keys_dev(rp_ring *r, const rp_ring_snap *before,
+                           const uint8_t *d_keys, const uint64_t *d_off, uint32_t stride, uint64_t n,
+                           int32_t nrep, uint32_t cap,
+                           uint32_t *d_idx, uint32_t *d_before, uint32_t *d_after, uint32_t *d_count,
+                           void *stream);
+int rp_ring_moved_keys(rp_ring *r, const rp_ring_snap *before, const char *keys, const uint64_t *off,
+                       uint32_t stride, uint64_t n, int32_t nrep, uint32_t cap,
+                       uint32_t *idx, uint32_t *before_rows, uint32_t *after_rows, uint32_t *count);
+/* Same with a caller hashFunc's key hashes (options.hashFunc, lib/ring/index.js:29). */
+int rp_ring_moved_hashes(rp_ring *r, const rp_ring_snap *before, const uint32_t *hashes, uint64_t n,
+                         int32_t nrep, uint32_t cap, uint32_t *idx, uint32_t *before_rows,
+                         uint32_t *after_rows, uint32_t *count);
+
 /* ------------------------------------------------------------------ Membership
  * Replaces the hot path of lib/membership/index.js Membership: update (249-324) with the
  * Member.evaluateUpdate rules (lib/membership/member.js:71-202) and computeChecksum /

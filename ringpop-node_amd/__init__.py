@@ -71,6 +71,13 @@ SIGNATURES = {
     "rp_ring_group_keys_dev": (_INT, [_P, _P, _P, _U32, _U64, _U32, _P, _P, _P, _P, _P]),
     "rp_ring_group_keys": (_INT, [_P, _P, _P, _U32, _U64, _U32, _P, _P, _P, _P]),
     "rp_ring_group_hashes": (_INT, [_P, _P, _U64, _U32, _P, _P, _P, _P]),
+    "rp_ring_snapshot": (_INT, [_P, _P]),
+    "rp_ring_snap_destroy": (_INT, [_P]),
+    "rp_ring_snap_info": (_INT, [_P, _P, _P, _P, _P]),
+    "rp_ring_snap_lookupn_dev": (_INT, [_P, _P, _P, _U32, _U64, _I32, _P, _P, _P]),
+    "rp_ring_moved_keys_dev": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _P, _P, _P, _P, _P]),
+    "rp_ring_moved_keys": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _P, _P, _P, _P]),
+    "rp_ring_moved_hashes": (_INT, [_P, _P, _P, _U64, _I32, _U32, _P, _P, _P, _P]),
     "rp_members_create": (_INT, [_U32, _INT, _P]),
     "rp_members_destroy": (_INT, [_P]),
     "rp_members_intern": (_INT, [_P, _P, _P, _U32, _P]),
@@ -482,12 +489,88 @@ class HashRing:
         check(lib().rp_ring_group_keys_dev(self._h, keys_ptr, off_ptr, stride, n, self_id, dests_ptr, goff_ptr,
                                            perm_ptr, ndest_ptr, stream))
 
+    # -- ring snapshots and moved keys (hand-off on ringChanged)
+    def snapshot(self):
+        """An immutable device copy of the ring as it is now (RingSnapshot); take one before
+        addRemoveServers and diff against it afterwards with movedKeys / moved_ids."""
+        h = ctypes.c_void_p()
+        check(lib().rp_ring_snapshot(self._h, ctypes.byref(h)))
+        return RingSnapshot(h)
+
+    def moved_ids(self, keys, before, n=1, cap=None):
+        """(idx, before_rows, after_rows): the indices (ascending) of the keys whose lookupN(key, n)
+        row under the snapshot `before` differs from the row now, and the two rows [m, max(n,1)]
+        (NULL_ID padded). cap bounds the entries returned; `moved_count` holds the full count."""
+        w = max(int(n), 1)
+        cnt = ctypes.c_uint32()
+        if self.hashFunc is not None:
+            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
+            k = len(hs)
+        else:
+            blob, off, stride, k = self._key_pack(keys)
+        c = k if cap is None else min(int(cap), k)
+        idx = np.empty(max(c, 1), dtype=np.uint32)
+        br = np.empty((max(c, 1), w), dtype=np.uint32)
+        ar = np.empty((max(c, 1), w), dtype=np.uint32)
+        if self.hashFunc is not None:
+            check(lib().rp_ring_moved_hashes(self._h, before._h, hs.ctypes.data, k, int(n), c, idx.ctypes.data,
+                                             br.ctypes.data, ar.ctypes.data, ctypes.byref(cnt)))
+        else:
+            check(lib().rp_ring_moved_keys(self._h, before._h, blob.ctypes.data, _ptr(off), stride, k, int(n), c,
+                                           idx.ctypes.data, br.ctypes.data, ar.ctypes.data, ctypes.byref(cnt)))
+        self.moved_count = cnt.value
+        m = min(cnt.value, c)
+        return idx[:m], br[:m], ar[:m]
+
+    def movedKeys(self, keys, before, n=1):
+        """[(key, [owner names before], [owner names now])] for every key whose lookupN(key, n)
+        changed since the snapshot `before`, in input order."""
+        keys = [k if isinstance(k, (bytes, np.ndarray)) else str(k) for k in keys]
+        idx, br, ar = self.moved_ids(keys, before, n)
+        return [(keys[i], [self.name(x) for x in b if x != NULL_ID], [self.name(x) for x in a if x != NULL_ID])
+                for i, b, a in zip(idx, br, ar)]
+
+    def moved_dev(self, before, keys_ptr, n, nrep, cap, idx_ptr, before_ptr, after_ptr, count_ptr, stride=36,
+                  off_ptr=None, stream=None):
+        check(lib().rp_ring_moved_keys_dev(self._h, before._h, keys_ptr, off_ptr, stride, n, nrep, cap, idx_ptr,
+                                           before_ptr, after_ptr, count_ptr, stream))
+
     # -- device-resident hot path (pointers from torch tensors / hipMalloc)
     def lookupn_dev(self, keys_ptr, n, nrep, owners_ptr, counts_ptr=None, stride=36, off_ptr=None, stream=None):
         check(lib().rp_ring_lookupn_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, owners_ptr, counts_ptr, stream))
 
     def lookup_dev(self, keys_ptr, n, owners_ptr, stride=36, off_ptr=None, stream=None):
         check(lib().rp_ring_lookup_dev(self._h, keys_ptr, off_ptr, stride, n, owners_ptr, stream))
+
+
+class RingSnapshot:
+    """rp_ring_snap: an immutable device copy of a HashRing's lookup state (HashRing.snapshot()).
+    Owner ids are the ring's; it outlives later ring changes and the ring itself."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            return lib().rp_ring_snap_destroy(h)
+        return 0
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{'tokens', 'servers', 'checksum'} as of the snapshot (checksum None while unset)."""
+        m, sc, ck, st = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int()
+        check(lib().rp_ring_snap_info(self._h, ctypes.byref(m), ctypes.byref(sc), ctypes.byref(ck), ctypes.byref(st)))
+        return {"tokens": m.value, "servers": sc.value, "checksum": ck.value if st.value else None}
+
+    def lookupn_dev(self, keys_ptr, n, nrep, owners_ptr, counts_ptr=None, stride=36, off_ptr=None, stream=None):
+        check(lib().rp_ring_snap_lookupn_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, owners_ptr, counts_ptr,
+                                             stream))
 
 
 class DampConfig(ctypes.Structure):

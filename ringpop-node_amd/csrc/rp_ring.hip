@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -3208,12 +3209,283 @@ static void group_keys(Ring& r, const uint8_t* keys, const uint64_t* off, uint32
     RP_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------- ring snapshots and moved keys
+// A snapshot is a device copy of the exact wide arrays (RingView) with the counts and checksum of
+// its moment. k_moved diffs two rings over one key stream: each key is read and hashed once, both
+// rings are searched and walked from that hash on their exact views (moved_find / moved_walk; no
+// fingerprints, so no key is ever deferred), the two rows are compared in registers, and only the moved keys leave the
+// kernel. Order-preserving compaction in one launch: wave ballots + popcounts, per-workgroup
+// totals in LDS, and the tile's global offset by decoupled look-back (tile = ticket, so tiles are
+// in key order and every tile a tile waits on is already running).
+struct Snap {
+    int device = 0;
+    DevBuf<uint32_t> tok, own, bstart;
+    uint32_t M = 0, bbits = 8, server_count = 0, checksum = 0;
+    bool has_checksum = false;
+    RingView view() const { return RingView{tok.p, own.p, bstart.p, M, 32u - bbits}; }
+};
+
+// Exact search and walk on the wide arrays with one load instruction per step, as the lean kernel
+// does on the compact layout (every lane of a load instruction that touches another line is one
+// L1->L2 request, and the lookups are bound by those): the bucket's [lo, hi) as one 8-B load, its
+// tokens four at a time as one 16-B load (buckets hold ~4 tokens), the successor owners four at a
+// time as one 16-B load. Every load stays inside [0, M); windows that would cross M fall back to
+// single loads. Results equal RingView::find + ring_walk exactly.
+__device__ __forceinline__ uint32_t moved_find(const RingView& rv, uint32_t h) {
+    const uint32_t b = h >> rv.shift;
+    const u32x2_a4 be = *reinterpret_cast<const u32x2_a4*>(rv.bstart + b);
+    uint32_t lo = be.x, hi = be.y;
+    if (hi - lo > 16) {  // a crowded bucket (caller hashFunc values that collide): binary search
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (rv.tok[mid] < h) lo = mid + 1;
+            else hi = mid;
+        }
+        return lo;
+    }
+    while (lo < hi) {
+        const uint32_t n = hi - lo < 4u ? hi - lo : 4u;
+        uint32_t c;
+        if (lo + 4u <= rv.M) {
+            const u32x4_a4 t = *reinterpret_cast<const u32x4_a4*>(rv.tok + lo);
+            c = (uint32_t)(t.x < h) + (uint32_t)((n > 1u) & (t.y < h)) + (uint32_t)((n > 2u) & (t.z < h)) +
+                (uint32_t)((n > 3u) & (t.w < h));  // (sorted: the tokens below h are a prefix)
+        } else {
+            c = 0;
+            while (c < n && rv.tok[lo + c] < h) c++;
+        }
+        lo += c;
+        if (c < 4u) break;
+    }
+    return lo;
+}
+
+template <int MAXN>
+__device__ __forceinline__ void moved_walk(const RingView& rv, uint32_t i, int np, uint32_t (&res)[MAXN]) {
+#pragma unroll
+    for (int q = 0; q < MAXN; q++) res[q] = NIL;
+    if (rv.M == 0) return;
+    if (np <= 0) {
+        if (i < rv.M) res[0] = rv.own[i];
+        return;
+    }
+    uint32_t j = (i == rv.M) ? 0u : i;
+    if (MAXN == 1) {
+        res[0] = rv.own[j];
+        return;
+    }
+    int cnt = 0;
+    auto take = [&](uint32_t o) {
+        bool dup = false;
+#pragma unroll
+        for (int q = 0; q < MAXN; q++) dup |= (q < cnt) & (res[q] == o);
+        if (!dup) {
+#pragma unroll
+            for (int q = 0; q < MAXN; q++) res[q] = (q == cnt) ? o : res[q];
+            cnt++;
+        }
+    };
+    uint32_t steps = 0;
+    while (steps < rv.M && cnt < np) {
+        if (j + 4u <= rv.M) {
+            const u32x4_a4 o = *reinterpret_cast<const u32x4_a4*>(rv.own + j);
+            const uint32_t o4[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (steps < rv.M && cnt < np) {
+                    take(o4[k]);
+                    steps++;
+                }
+            j = (j + 4u == rv.M) ? 0u : j + 4u;
+        } else {
+            take(rv.own[j]);
+            steps++;
+            j = (j + 1u == rv.M) ? 0u : j + 1u;
+        }
+    }
+}
+
+// FIXED: 36-byte keys at stride 36 from a 4-byte aligned base; full tiles of a 16-byte aligned
+// base stream through LDS with non-temporal 16-B loads (read once; they must not evict the two
+// rings' tables from L2). Otherwise: per-thread byte fetches (offsets, any stride, any base) or
+// precomputed hashes. One tile of 256 * KPL keys per workgroup, key q * 256 + tid of the tile in
+// slot q of thread tid, so that (q, wave, lane) order is key order.
+template <int MAXN, int KPL, bool FIXED>
+__global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict__ keys,
+                                                      const uint64_t* __restrict__ off, uint32_t stride,
+                                                      const uint32_t* __restrict__ hashes, uint32_t n, RingView bv,
+                                                      int npb, RingView av, int npa, uint32_t W, uint32_t cap,
+                                                      uint32_t* __restrict__ idx, uint32_t* __restrict__ brow,
+                                                      uint32_t* __restrict__ arow, uint32_t* __restrict__ count,
+                                                      uint64_t* __restrict__ lb, unsigned long long* ctr,
+                                                      uint64_t tag, uint32_t ntiles, uint32_t* err) {
+    constexpr int TILE = kLkThreads * KPL;
+    constexpr int W4 = 9;                    // dwords per 36-byte key
+    constexpr int V4 = TILE * W4 / 4;        // 16-B vectors per full tile
+    constexpr int PER = (V4 + kLkThreads - 1) / kLkThreads;
+    static_assert((TILE * W4) % 4 == 0, "tile must be a whole number of 16-B vectors");
+    __shared__ __attribute__((aligned(16))) uint32_t sk[FIXED ? TILE * W4 : 4];
+    __shared__ uint32_t s_cnt[KPL * (kLkThreads / 64)];
+    __shared__ uint32_t s_excl;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tile = take_unit(ctr, ntiles, err);  // (syncs)
+    if (tile >= ntiles) return;  // a ticket count out of step (reported): never write out of bounds
+    const uint32_t base = tile * (uint32_t)TILE;
+    const uint32_t cnt = n - base < (uint32_t)TILE ? n - base : (uint32_t)TILE;
+    if constexpr (FIXED) {
+        const uint8_t* src = keys + (uint64_t)base * 36u;
+        if (cnt == (uint32_t)TILE && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
+            const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+            u32x4* d4 = reinterpret_cast<u32x4*>(sk);
+            u32x4 pre[PER];
+#pragma unroll
+            for (int q = 0; q < PER; q++) {
+                const int k = tid + q * kLkThreads;
+                if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
+            }
+#pragma unroll
+            for (int q = 0; q < PER; q++) {
+                const int k = tid + q * kLkThreads;
+                if (k < V4) d4[k] = pre[q];
+            }
+        } else {
+            const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
+            for (uint32_t k = tid; k < cnt * W4; k += kLkThreads) sk[k] = s1[k];
+        }
+        __syncthreads();
+    }
+    uint32_t rb[KPL][MAXN], ra[KPL][MAXN];
+    bool mv[KPL];
+#pragma unroll
+    for (int q = 0; q < KPL; q++) {
+        const uint32_t kl = (uint32_t)(q * kLkThreads + tid);
+        mv[q] = false;
+#pragma unroll
+        for (int j = 0; j < MAXN; j++) rb[q][j] = ra[q][j] = NIL;
+        if (kl < cnt) {
+            uint32_t h;
+            if constexpr (FIXED) {
+                uint32_t w[W4];
+#pragma unroll
+                for (int j = 0; j < W4; j++) w[j] = sk[kl * W4 + j];
+                h = fh::hash32_words<36>(w);
+            } else if (hashes) {
+                h = hashes[base + kl];
+            } else {
+                const uint64_t k = (uint64_t)base + kl;
+                uint64_t b, e;
+                if (stride) {
+                    b = k * stride;
+                    e = b + stride;
+                } else {
+                    b = off[k];
+                    e = off[k + 1];
+                }
+                h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
+            }
+            moved_walk<MAXN>(bv, moved_find(bv, h), npb, rb[q]);
+            moved_walk<MAXN>(av, moved_find(av, h), npa, ra[q]);
+            bool d = false;
+#pragma unroll
+            for (int j = 0; j < MAXN; j++) d |= rb[q][j] != ra[q][j];
+            mv[q] = d;
+        }
+    }
+    // ranks inside the wave's 64 keys of slot q, and the (slot, wave) segment totals
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t rank[KPL];
+#pragma unroll
+    for (int q = 0; q < KPL; q++) {
+        const uint64_t m = __ballot(mv[q]);
+        rank[q] = (uint32_t)__popcll(m & lt_mask);
+        if (lane == 0) s_cnt[q * (kLkThreads / 64) + wave] = (uint32_t)__popcll(m);
+    }
+    __syncthreads();
+    uint32_t pre[KPL], total = 0;
+#pragma unroll
+    for (int s = 0; s < KPL * (kLkThreads / 64); s++) {
+        if ((s & (kLkThreads / 64 - 1)) == wave) pre[s / (kLkThreads / 64)] = total;
+        total += s_cnt[s];
+    }
+    if (tid == 0) lb_store(lb + tile, tag | (tile == 0 ? kLbP : kLbA) | total);
+    if (tid < 64) {
+        const uint32_t excl = lookback_wave(lb, tile, tag, err);
+        if (tid == 0) {
+            if (tile > 0) lb_store(lb + tile, tag | kLbP | (excl + total));
+            s_excl = excl;
+            if (tile == ntiles - 1) *count = excl + total;
+        }
+    }
+    __syncthreads();
+    const uint32_t gbase = s_excl;
+#pragma unroll
+    for (int q = 0; q < KPL; q++) {
+        const uint32_t p = gbase + pre[q] + rank[q];
+        if (mv[q] && p < cap) {  // (also bounds every write if a look-back wait gave up)
+            idx[p] = base + (uint32_t)(q * kLkThreads + tid);
+#pragma unroll
+            for (int j = 0; j < MAXN; j++) {
+                if ((uint32_t)j < W) {
+                    if (brow) brow[(uint64_t)p * W + j] = rb[q][j];
+                    if (arow) arow[(uint64_t)p * W + j] = ra[q][j];
+                }
+            }
+        }
+    }
+}
+
+template <int MAXN, int KPL, bool FIXED, class... A>
+static void launch_moved_k(uint32_t n, hipStream_t st, Scratch& ws, A... args) {
+    const uint32_t ntiles = (uint32_t)(((uint64_t)n + kLkThreads * KPL - 1) / (kLkThreads * KPL));
+    const LookBack L = lookback_prepare(ws, ntiles, st);
+    hipLaunchKernelGGL((k_moved<MAXN, KPL, FIXED>), dim3(ntiles), dim3(kLkThreads), 0, st, args..., L.words, L.ticket,
+                       L.tag, ntiles, L.err);
+    RP_HIP(hipGetLastError());
+}
+
+// before / after rows of W slots each; outputs as rp_ring_moved_keys_dev documents
+static void moved_keys(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t* off, uint32_t stride,
+                       const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t cap, uint32_t* idx, uint32_t* brow,
+                       uint32_t* arow, uint32_t* count, hipStream_t st) {
+    RP_REQUIRE(nrep <= 8, "moved_keys: nrep is at most 8 (the rows are compared in registers)");
+    RP_REQUIRE(n < (1ull << 32), "moved_keys: at most 2^32-1 keys per call");
+    RP_REQUIRE(s.device == r.device, "moved_keys: the snapshot lives on another device");
+    RP_REQUIRE(count, "moved_keys: null count");
+    RP_REQUIRE(cap == 0 || idx, "moved_keys: null index buffer");
+    // the ring is rebuilt on r.st; make the caller's stream wait for it
+    if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
+    if (n == 0 || (r.M == 0 && s.M == 0)) {
+        RP_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+        return;
+    }
+    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const int npb = (int)std::min<int64_t>(nrep, s.server_count), npa = (int)std::min<int64_t>(nrep, r.server_count);
+    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
+    const RingView bv = s.view(), av = r.view();
+#define RP_MOVED(MAXN, KPL, FIXED)                                                                                  \
+    launch_moved_k<MAXN, KPL, FIXED>((uint32_t)n, st, r.ws, keys, off, stride, hashes, (uint32_t)n, bv, npb, av, npa, \
+                                     W, cap, idx, brow, arow, count)
+    if (fixed36) {
+        if (W == 1) RP_MOVED(1, 4, true);
+        else if (W <= 4) RP_MOVED(4, 4, true);
+        else RP_MOVED(8, 2, true);
+    } else {
+        if (W == 1) RP_MOVED(1, 1, false);
+        else if (W <= 4) RP_MOVED(4, 1, false);
+        else RP_MOVED(8, 1, false);
+    }
+#undef RP_MOVED
+}
+
 }  // namespace rp
 
 // ==================================================================================== C ABI
 
 struct rp_ring {
     rp::Ring impl;
+};
+struct rp_ring_snap {
+    rp::Snap impl;
 };
 
 using rp::guard;
@@ -3814,6 +4086,157 @@ int rp_ring_group_hashes(rp_ring* h, const uint32_t* hashes, uint64_t n, uint32_
         rp::Ring& r = R(h);
         RP_REQUIRE(n == 0 || hashes, "group_hashes: null hash buffer");
         host_group(r, nullptr, nullptr, 0, hashes, n, self_id, dests, group_off, perm, ndest);
+    });
+}
+
+// ---- ring snapshots and moved keys
+
+int rp_ring_snapshot(rp_ring* h, rp_ring_snap** out) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        RP_REQUIRE(out, "snapshot: out is null");
+        svc_stop(r);
+        std::unique_ptr<rp_ring_snap> s(new rp_ring_snap());
+        rp::Snap& d = s->impl;
+        d.device = r.device;
+        d.M = r.M;
+        d.bbits = r.bbits;
+        d.server_count = r.server_count;
+        d.checksum = r.checksum;
+        d.has_checksum = r.has_checksum;
+        const uint64_t nbk = (1ull << r.bbits) + 1;
+        d.tok.reserve(r.M);
+        d.own.reserve(r.M);
+        d.bstart.reserve(nbk);
+        if (r.M) {
+            RP_HIP(hipMemcpyAsync(d.tok.p, r.tok.p, 4ull * r.M, hipMemcpyDeviceToDevice, r.st));
+            RP_HIP(hipMemcpyAsync(d.own.p, r.own.p, 4ull * r.M, hipMemcpyDeviceToDevice, r.st));
+        }
+        RP_HIP(hipMemcpyAsync(d.bstart.p, r.bstart.p, 4ull * nbk, hipMemcpyDeviceToDevice, r.st));
+        RP_HIP(hipStreamSynchronize(r.st));  // complete before any later rebuild or any caller stream reads it
+        *out = s.release();
+    });
+}
+
+int rp_ring_snap_destroy(rp_ring_snap* s) {
+    return guard([&] {  // (the buffers' hipFree synchronizes the device: no resident service meanwhile)
+        if (!s) return;
+        (void)hipSetDevice(s->impl.device);
+        delete s;
+    });
+}
+
+int rp_ring_snap_info(const rp_ring_snap* s, uint32_t* token_count, uint32_t* server_count, uint32_t* checksum,
+                      int* checksum_is_set) {
+    return guard_host([&] {
+        RP_REQUIRE(s, "null snapshot handle");
+        if (token_count) *token_count = s->impl.M;
+        if (server_count) *server_count = s->impl.server_count;
+        if (checksum) *checksum = s->impl.checksum;
+        if (checksum_is_set) *checksum_is_set = s->impl.has_checksum ? 1 : 0;
+    });
+}
+
+int rp_ring_snap_lookupn_dev(rp_ring_snap* s, const uint8_t* d_keys, const uint64_t* d_off, uint32_t stride,
+                             uint64_t n, int32_t nrep, uint32_t* d_owners, uint8_t* d_counts, void* stream) {
+    return guard([&] {
+        RP_REQUIRE(s, "null snapshot handle");
+        RP_REQUIRE(n == 0 || (d_keys && d_owners && (stride || d_off)), "snap_lookupn_dev: null buffer");
+        if (n == 0) return;
+        RP_HIP(hipSetDevice(s->impl.device));
+        const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+        const int np = (int)std::min<int64_t>(nrep, s->impl.server_count);  // lib/ring/index.js:159-162
+        rp::launch_lookupn_view(s->impl.view(), d_keys, d_off, stride, nullptr, n, np, W, d_owners, d_counts,
+                                rp::as_stream(stream));
+    });
+}
+
+static const rp::Snap& S(const rp_ring_snap* s) {
+    if (!s) throw rp::Error(rp::RP_EINVAL, "null snapshot handle");
+    return s->impl;
+}
+
+int rp_ring_moved_keys_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t* d_keys, const uint64_t* d_off,
+                           uint32_t stride, uint64_t n, int32_t nrep, uint32_t cap, uint32_t* d_idx,
+                           uint32_t* d_before, uint32_t* d_after, uint32_t* d_count, void* stream) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "moved_keys_dev: null key buffer");
+        svc_stop(r);
+        rp::moved_keys(r, s, d_keys, d_off, stride, nullptr, n, nrep, cap, d_idx, d_before, d_after, d_count,
+                       rp::as_stream(stream));
+    });
+}
+
+// host-buffer forms: keys (or a caller hashFunc's key hashes) in, the moved list out
+static void host_moved(rp::Ring& r, const rp::Snap& s, const char* keys, const uint64_t* off, uint32_t stride,
+                       const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t cap, uint32_t* idx, uint32_t* brows,
+                       uint32_t* arows, uint32_t* count) {
+    RP_REQUIRE(count, "moved_keys: null count");
+    RP_REQUIRE(nrep <= 8, "moved_keys: nrep is at most 8 (the rows are compared in registers)");
+    RP_REQUIRE(n < (1ull << 32), "moved_keys: at most 2^32-1 keys per call");
+    RP_REQUIRE(cap == 0 || n == 0 || idx, "moved_keys: null index buffer");
+    svc_stop(r);
+    const uint8_t* dk = nullptr;
+    const uint64_t* doff = nullptr;
+    const uint32_t* dh = nullptr;
+    if (n && hashes) {
+        r.io_a.reserve(n);
+        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
+        dh = r.io_a.p;
+    } else if (n) {
+        const uint64_t bytes = stride ? n * stride : off[n];
+        r.io_keys.reserve(bytes + 16);
+        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
+        dk = r.io_keys.p;
+        if (!stride) {
+            r.io_off.reserve(n + 1);
+            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
+            doff = r.io_off.p;
+        }
+    }
+    // io_b = [count 1 | idx c | before rows c*W | after rows c*W], c = min(cap, n)
+    const uint64_t c = std::min<uint64_t>(cap, n), W = nrep > 1 ? (uint64_t)nrep : 1u;
+    r.io_b.reserve(1 + c * (1 + 2 * W));
+    uint32_t* dcount = r.io_b.p;
+    uint32_t* didx = dcount + 1;
+    uint32_t* dbr = didx + c;
+    uint32_t* dar = dbr + c * W;
+    rp::moved_keys(r, s, dk, doff, stride, dh, n, nrep, (uint32_t)c, c ? didx : nullptr, brows ? dbr : nullptr,
+                   arows ? dar : nullptr, dcount, r.st);
+    uint32_t total = 0;
+    RP_HIP(hipMemcpyAsync(&total, dcount, 4, hipMemcpyDeviceToHost, r.st));
+    RP_HIP(hipStreamSynchronize(r.st));
+    rp::scratch_check(r.ws, r.st);  // a look-back wait that gave up is an error, not a wrong list
+    *count = total;
+    const uint64_t m = std::min<uint64_t>(total, c);
+    if (m) {
+        RP_HIP(hipMemcpyAsync(idx, didx, m * 4, hipMemcpyDeviceToHost, r.st));
+        if (brows) RP_HIP(hipMemcpyAsync(brows, dbr, m * W * 4, hipMemcpyDeviceToHost, r.st));
+        if (arows) RP_HIP(hipMemcpyAsync(arows, dar, m * W * 4, hipMemcpyDeviceToHost, r.st));
+        RP_HIP(hipStreamSynchronize(r.st));
+    }
+}
+
+int rp_ring_moved_keys(rp_ring* h, const rp_ring_snap* before, const char* keys, const uint64_t* off, uint32_t stride,
+                       uint64_t n, int32_t nrep, uint32_t cap, uint32_t* idx, uint32_t* before_rows,
+                       uint32_t* after_rows, uint32_t* count) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(n == 0 || (keys && (stride || off)), "moved_keys: null key buffer");
+        host_moved(r, s, keys, off, stride, nullptr, n, nrep, cap, idx, before_rows, after_rows, count);
+    });
+}
+
+int rp_ring_moved_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_t* hashes, uint64_t n, int32_t nrep,
+                         uint32_t cap, uint32_t* idx, uint32_t* before_rows, uint32_t* after_rows, uint32_t* count) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(n == 0 || hashes, "moved_hashes: null hash buffer");
+        host_moved(r, s, nullptr, nullptr, 0, hashes, n, nrep, cap, idx, before_rows, after_rows, count);
     });
 }
 

@@ -239,6 +239,39 @@ HashRing.prototype.lookupKeys = function lookupKeys(keys, whoami) {
     return g.dests.map(function (d) { return d === null ? whoami : d; });
 };
 
+// Hand-off on ringChanged: snapshot() before addRemoveServers, movedKeys(keys, snap, n) after it,
+// snap.destroy() when done. A snapshot is an immutable device copy of the ring; it stays valid
+// across later ring changes (and the ring's own destroy()).
+function RingSnapshot(h) { this._h = h; }
+RingSnapshot.prototype.destroy = function destroy() { native.destroy(this._h); };  // twice is harmless
+RingSnapshot.prototype.info = function info() { return native.ringSnapInfo(this._h); };
+
+HashRing.prototype.snapshot = function snapshot() {
+    return new RingSnapshot(native.ringSnapshot(this._h));
+};
+
+// The keys whose lookupN(key, n) differs between the snapshot and the ring now, in one device
+// pass: {count, idx, before, after} as Uint32Arrays (ascending key indices; rows of max(n,1)
+// owner ids, 0xFFFFFFFF = none). movedNames() turns that into [{key, before: [names], after:
+// [names]}].
+HashRing.prototype.movedKeys = function movedKeys(keys, snap, n) {
+    n = n === undefined ? 1 : n | 0;
+    return native.ringMovedKeys(this._h, this._customHash ? this._hashes(keys) : keys, snap._h, n);
+};
+
+HashRing.prototype.movedNames = function movedNames(keys, moved, n) {
+    var w = n > 1 ? n : 1, out = new Array(moved.idx.length), self = this;
+    function row(a, j) {
+        var r = [];
+        for (var q = 0; q < w && a[j * w + q] !== 0xFFFFFFFF; q++) { r.push(self.ownerName(a[j * w + q])); }
+        return r;
+    }
+    for (var j = 0; j < out.length; j++) {
+        out[j] = {key: keys[moved.idx[j]], before: row(moved.before, j), after: row(moved.after, j)};
+    }
+    return out;
+};
+
 // Id-level batch over precomputed key hashes: {owners: Uint32Array(ids, rows of max(n,1)),
 // counts: Uint8Array}; ownerName(id) maps ids back to server names.
 HashRing.prototype.lookupNHashes = function lookupNHashes(hashes, n) {
@@ -351,6 +384,7 @@ GossipSim.prototype.stats = function stats() { return native.simStats(this._h); 
 
 module.exports = {
     HashRing: HashRing,
+    RingSnapshot: RingSnapshot,
     MembershipMerge: MembershipMerge,
     GossipSim: GossipSim,
     hash32: native.hash32,
