@@ -197,6 +197,42 @@ int rp_ring_moved_hashes(rp_ring *r, const rp_ring_snap *before, const uint32_t 
                          int32_t nrep, uint32_t cap, uint32_t *idx, uint32_t *before_rows,
                          uint32_t *after_rows, uint32_t *count);
 
+/* Owner load and hash-space share: how many keys each server carries, as primary and as the 2nd
+ * to n-th replica, and which share of the 2^32 hash values it owns (the expected load).
+ * One past the largest server id this ring has interned (ids of removed servers included). */
+int rp_ring_id_bound(rp_ring *r, uint32_t *out);
+
+/* Owner load: load[id * W + q] = number of keys whose lookupN(key, nrep) row has server `id` in
+ * slot q; W = max(nrep, 1). The rows are exactly what rp_ring_lookupn* writes. RP_NULL_ID
+ * padding is not counted. load has id_cap * W entries. id_cap < rp_ring_id_bound is RP_EINVAL
+ * with nothing written. accumulate = 0: load is overwritten. Nonzero: the counts are added to
+ * what load holds, so a key set can be fed in batches. Any n (uint64). Any nrep that
+ * rp_ring_lookupn_dev accepts. An empty ring counts nothing.
+ * The keys are looked up in chunks of RP_LOAD_CHUNK keys (default 2^24) into a scratch the handle
+ * owns (chunk * W * 4 bytes, whatever n is), and each chunk's rows are counted on the same
+ * stream. The _dev form is stream-ordered and never syncs with the host, except that a stream
+ * other than the ring's own first waits for the ring's pending rebuilds (as rp_ring_lookupn_dev
+ * does). */
+int rp_ring_owner_load_dev(rp_ring *r, const uint8_t *d_keys, const uint64_t *d_off, uint32_t stride,
+                           uint64_t n, int32_t nrep, uint32_t id_cap, int accumulate,
+                           uint64_t *d_load, void *stream);
+int rp_ring_owner_load(rp_ring *r, const char *keys, const uint64_t *off, uint32_t stride, uint64_t n,
+                       int32_t nrep, uint32_t id_cap, uint64_t *load);          /* host buffers, overwrites */
+int rp_ring_owner_load_hashes(rp_ring *r, const uint32_t *hashes, uint64_t n, int32_t nrep,
+                              uint32_t id_cap, uint64_t *load);                 /* caller hashFunc */
+/* The same under a snapshot's ring (ids are the ring's interned ids; the id bound is the ring's
+ * at snapshot time). The snapshot allocates its row scratch at first use. */
+int rp_ring_snap_owner_load_dev(rp_ring_snap *s, const uint8_t *d_keys, const uint64_t *d_off, uint32_t stride,
+                                uint64_t n, int32_t nrep, uint32_t id_cap, int accumulate,
+                                uint64_t *d_load, void *stream);
+
+/* Hash-space share: share[id] = how many of the 2^32 hash values h have lookup(h) == id
+ * (lib/ring/index.js:145-154: the first token >= h, else the smallest token). The shares sum to
+ * 2^32 on a non-empty ring and are all 0 on an empty one. Host output, id_cap entries.
+ * id_cap is checked as above. */
+int rp_ring_owner_share(rp_ring *r, uint32_t id_cap, uint64_t *share);
+int rp_ring_snap_owner_share(rp_ring_snap *s, uint32_t id_cap, uint64_t *share);
+
 /* ------------------------------------------------------------------ Membership
  * Replaces the hot path of lib/membership/index.js Membership: update (249-324) with the
  * Member.evaluateUpdate rules (lib/membership/member.js:71-202) and computeChecksum /

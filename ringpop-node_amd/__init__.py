@@ -78,6 +78,13 @@ SIGNATURES = {
     "rp_ring_moved_keys_dev": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _P, _P, _P, _P, _P]),
     "rp_ring_moved_keys": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _P, _P, _P, _P]),
     "rp_ring_moved_hashes": (_INT, [_P, _P, _P, _U64, _I32, _U32, _P, _P, _P, _P]),
+    "rp_ring_id_bound": (_INT, [_P, _P]),
+    "rp_ring_owner_load_dev": (_INT, [_P, _P, _P, _U32, _U64, _I32, _U32, _INT, _P, _P]),
+    "rp_ring_owner_load": (_INT, [_P, _P, _P, _U32, _U64, _I32, _U32, _P]),
+    "rp_ring_owner_load_hashes": (_INT, [_P, _P, _U64, _I32, _U32, _P]),
+    "rp_ring_snap_owner_load_dev": (_INT, [_P, _P, _P, _U32, _U64, _I32, _U32, _INT, _P, _P]),
+    "rp_ring_owner_share": (_INT, [_P, _U32, _P]),
+    "rp_ring_snap_owner_share": (_INT, [_P, _U32, _P]),
     "rp_members_create": (_INT, [_U32, _INT, _P]),
     "rp_members_destroy": (_INT, [_P]),
     "rp_members_intern": (_INT, [_P, _P, _P, _U32, _P]),
@@ -495,7 +502,7 @@ class HashRing:
         addRemoveServers and diff against it afterwards with movedKeys / moved_ids."""
         h = ctypes.c_void_p()
         check(lib().rp_ring_snapshot(self._h, ctypes.byref(h)))
-        return RingSnapshot(h)
+        return RingSnapshot(h, self.id_bound())
 
     def moved_ids(self, keys, before, n=1, cap=None):
         """(idx, before_rows, after_rows): the indices (ascending) of the keys whose lookupN(key, n)
@@ -535,6 +542,55 @@ class HashRing:
         check(lib().rp_ring_moved_keys_dev(self._h, before._h, keys_ptr, off_ptr, stride, n, nrep, cap, idx_ptr,
                                            before_ptr, after_ptr, count_ptr, stream))
 
+    # -- owner load and hash-space share (how even is the ring?)
+    def id_bound(self):
+        """One past the largest server id the ring has interned (removed servers included)."""
+        v = ctypes.c_uint32()
+        check(lib().rp_ring_id_bound(self._h, ctypes.byref(v)))
+        return v.value
+
+    def owner_load_ids(self, keys, n=1):
+        """np.uint64[id_bound, max(n,1)]: [id, q] = how many keys have server id in slot q of their
+        lookupN(key, n) row (q = 0: as primary)."""
+        if self.hashFunc is not None:
+            return self.owner_load_hashes(np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32), n)
+        blob, off, stride, k = self._key_pack(keys)
+        cap, w = self.id_bound(), max(int(n), 1)
+        out = np.zeros((cap, w), dtype=np.uint64)
+        check(lib().rp_ring_owner_load(self._h, blob.ctypes.data, _ptr(off), stride, k, int(n), cap,
+                                       out.ctypes.data if cap else None))
+        return out
+
+    def owner_load_hashes(self, hashes, n=1):
+        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
+        cap, w = self.id_bound(), max(int(n), 1)
+        out = np.zeros((cap, w), dtype=np.uint64)
+        check(lib().rp_ring_owner_load_hashes(self._h, hs.ctypes.data, len(hs), int(n), cap,
+                                              out.ctypes.data if cap else None))
+        return out
+
+    def owner_load_dev(self, keys_ptr, n, nrep, load_ptr, id_cap, accumulate=False, stride=36, off_ptr=None,
+                       stream=None):
+        check(lib().rp_ring_owner_load_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, id_cap, int(bool(accumulate)),
+                                           load_ptr, stream))
+
+    def ownerLoad(self, keys, n=1):
+        """{server name: [key count per lookupN slot]} for the servers now in the ring."""
+        load = self.owner_load_ids([k if isinstance(k, (bytes, np.ndarray)) else str(k) for k in keys], n)
+        return {s: [int(x) for x in load[self.server_id(s)]] for s in self._servers}
+
+    def owner_share_ids(self):
+        """np.uint64[id_bound]: how many of the 2^32 hash values each server id owns."""
+        cap = self.id_bound()
+        out = np.zeros(cap, dtype=np.uint64)
+        check(lib().rp_ring_owner_share(self._h, cap, out.ctypes.data if cap else None))
+        return out
+
+    def ownerShare(self):
+        """{server name: owned hash values} (they sum to 2^32 on a non-empty ring)."""
+        share = self.owner_share_ids()
+        return {s: int(share[self.server_id(s)]) for s in self._servers}
+
     # -- device-resident hot path (pointers from torch tensors / hipMalloc)
     def lookupn_dev(self, keys_ptr, n, nrep, owners_ptr, counts_ptr=None, stride=36, off_ptr=None, stream=None):
         check(lib().rp_ring_lookupn_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, owners_ptr, counts_ptr, stream))
@@ -547,8 +603,13 @@ class RingSnapshot:
     """rp_ring_snap: an immutable device copy of a HashRing's lookup state (HashRing.snapshot()).
     Owner ids are the ring's; it outlives later ring changes and the ring itself."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, id_bound=0):
         self._h = handle
+        self._id_bound = id_bound
+
+    def id_bound(self):
+        """The ring's id_bound() at snapshot time (a method, as on HashRing)."""
+        return self._id_bound
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
@@ -571,6 +632,20 @@ class RingSnapshot:
     def lookupn_dev(self, keys_ptr, n, nrep, owners_ptr, counts_ptr=None, stride=36, off_ptr=None, stream=None):
         check(lib().rp_ring_snap_lookupn_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, owners_ptr, counts_ptr,
                                              stream))
+
+    def owner_load_dev(self, keys_ptr, n, nrep, load_ptr, id_cap, accumulate=False, stride=36, off_ptr=None,
+                       stream=None):
+        """HashRing.owner_load_dev under the snapshotted ring."""
+        check(lib().rp_ring_snap_owner_load_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, id_cap,
+                                                int(bool(accumulate)), load_ptr, stream))
+
+    def owner_share_ids(self, id_cap=None):
+        """np.uint64[id_cap]: the snapshotted ring's hash-space share per server id (id_cap: the
+        ring's id bound at snapshot time, or more)."""
+        cap = self.id_bound() if id_cap is None else int(id_cap)
+        out = np.zeros(cap, dtype=np.uint64)
+        check(lib().rp_ring_snap_owner_share(self._h, cap, out.ctypes.data if cap else None))
+        return out
 
 
 class DampConfig(ctypes.Structure):

@@ -145,4 +145,29 @@ struct DevBuf {
     }
 };
 
+// Orders the uses of a handle's device scratch across streams: a use on another stream than the
+// previous one first waits (on the device) for everything queued on that stream so far. The
+// previous stream must still exist at the next use (a stream is destroyed only after the handles
+// that ran on it are done with it or destroyed).
+struct StreamOrder {
+    hipStream_t last_st = nullptr;
+    hipEvent_t ev = nullptr;
+    bool used = false;
+    StreamOrder() = default;
+    StreamOrder(const StreamOrder&) = delete;
+    StreamOrder& operator=(const StreamOrder&) = delete;
+    ~StreamOrder() {
+        if (ev) (void)hipEventDestroy(ev);
+    }
+    void use_on(hipStream_t st) {
+        if (used && st != last_st) {
+            if (!ev) RP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            RP_HIP(hipEventRecord(ev, last_st));
+            RP_HIP(hipStreamWaitEvent(st, ev, 0));
+        }
+        last_st = st;
+        used = true;
+    }
+};
+
 }  // namespace rp

@@ -28,26 +28,11 @@ struct Scratch {
     uint32_t epoch = 0;
     // the stream that last used this scratch: a launch on another stream first waits for it
     // (use_on), so two streams never interleave tickets or look-back words
-    hipStream_t last_st = nullptr;
-    hipEvent_t ev = nullptr;
-    bool used = false;
+    StreamOrder order;
     Scratch() = default;
     Scratch(const Scratch&) = delete;
     Scratch& operator=(const Scratch&) = delete;
-    ~Scratch() {
-        if (ev) (void)hipEventDestroy(ev);
-    }
-    // order this scratch's next use on `st` after everything queued on the stream that used it
-    // last
-    void use_on(hipStream_t st) {
-        if (used && st != last_st) {
-            if (!ev) RP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            RP_HIP(hipEventRecord(ev, last_st));
-            RP_HIP(hipStreamWaitEvent(st, ev, 0));
-        }
-        last_st = st;
-        used = true;
-    }
+    void use_on(hipStream_t st) { order.use_on(st); }
 };
 
 constexpr uint32_t kErrSpin = 1u, kErrTicket = 2u, kErrRange = 4u;  // kErrRange: a member incarnation past +-2^60 or status > 3

@@ -2432,6 +2432,15 @@ __global__ void k_gen_uuid(uint32_t seed, uint64_t k0, uint64_t n, uint32_t* __r
 
 // ---------------------------------------------------------------------------------- handle
 
+// The scratch of the owner-load calls of one handle (a ring or a snapshot), ordered across
+// streams as Scratch is: a call on another stream first waits for the previous call's work.
+struct LoadScratch {
+    DevBuf<uint32_t> rows;             // one chunk's rows
+    DevBuf<unsigned long long> out;    // the host forms' counters and the shares
+    StreamOrder order;
+    void use_on(hipStream_t st) { order.use_on(st); }
+};
+
 struct Ring {
     int device = 0;
     hipStream_t st = nullptr;
@@ -2497,6 +2506,7 @@ struct Ring {
     // group keys by owner (handleOrProxyAll)
     DevBuf<uint32_t> grp_own, grp_key, grp_first, grp_dk, grp_dv, grp_rank;
     Scratch ws;
+    LoadScratch load_ws;  // owner load / share
 
     RingView view() const {
         return RingView{tok.p, own.p, bstart.p, M, 32u - bbits};
@@ -3221,7 +3231,9 @@ struct Snap {
     int device = 0;
     DevBuf<uint32_t> tok, own, bstart;
     uint32_t M = 0, bbits = 8, server_count = 0, checksum = 0;
+    uint32_t id_bound = 0;  // the ring's interned ids at snapshot time (the owner-load id_cap check)
     bool has_checksum = false;
+    LoadScratch load_ws;  // owner load / share (allocated at first use)
     RingView view() const { return RingView{tok.p, own.p, bstart.p, M, 32u - bbits}; }
 };
 
@@ -3475,6 +3487,202 @@ static void moved_keys(Ring& r, const Snap& s, const uint8_t* keys, const uint64
         else RP_MOVED(8, 1, false);
     }
 #undef RP_MOVED
+}
+
+// ------------------------------------------------------------- owner load and hash-space share
+// load[id * W + q] = how many keys have server `id` in slot q of their lookupN row. The lookup
+// kernels are not forked: the key stream is walked in chunks, launch_lookupn / launch_lookupn_view
+// writes a chunk's rows into a handle-owned scratch (16-B aligned: the lean path), and k_owner_load
+// counts those rows on the same stream, so the rows are what rp_ring_lookupn* writes on every
+// layout, key form and nrep, and the extra memory is chunk * W * 4 bytes whatever n is.
+constexpr int kLoadThreads = 1024;
+constexpr uint32_t kLoadBins = 32768;         // uint32 LDS bins of one launch's window (128 KB of gfx950's 160 KB)
+constexpr uint32_t kLoadBins2 = 20480;        // at most this many LDS words: two workgroups share a CU (80 KB each)
+constexpr uint64_t kLoadChunk = 1ull << 24;   // keys a chunk (RP_LOAD_CHUNK): the best of the 2^20..2^24 sweep, DESIGN 4.2c
+constexpr uint64_t kLoadSlots = 1ull << 30;   // row slots a chunk at most: 32-bit slot indices in the kernel
+
+// One launch counts the slots of one chunk's rows that fall into the bin window [b0, b0 + nb) of
+// the flat bins id * W + q. Counts are privatised in LDS (uint32, LDS atomic adds) and flushed
+// once per workgroup. Invariant: a chunk has fewer than 2^31 row slots (kLoadSlots), so no uint32
+// LDS bin can overflow within one launch; the global counters are 64-bit because n is.
+// Few bins: with nb << the LDS words given, 2^cl copies of the window are kept (bin b of copy c
+// at word (b << cl) + c, c = lane & (2^cl - 1): with 64 copies every lane of a wave has a bank of
+// its own), so that the lanes of a wave do not serialise on a handful of words; the flush sums
+// the copies (rotated by the thread index, so that the threads of a wave read different banks).
+// Flush: thread t adds bin t, t + 1024, ...: a wave-instruction covers 64 contiguous 8-B
+// counters (512 contiguous bytes), minus the lanes whose bin is zero.
+// WT: the row width when it is 1..4 (a constant divisor for the slot's q), 0: any width.
+template <int WT>
+__global__ __launch_bounds__(kLoadThreads) void k_owner_load(const uint32_t* __restrict__ rows, uint32_t nslots,
+                                                             uint32_t Wrt, uint64_t b0, uint32_t nb, uint32_t cl,
+                                                             unsigned long long* __restrict__ load) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_bins[];
+    const uint32_t W = WT ? (uint32_t)WT : Wrt;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t copy = tid & ((1u << cl) - 1u);
+    const uint32_t words = nb << cl;
+    for (uint32_t i = tid; i < words; i += kLoadThreads) s_bins[i] = 0;
+    __syncthreads();
+    auto count = [&](uint32_t id, uint32_t q) {
+        if (id == NIL) return;
+        const uint64_t bin = (uint64_t)id * W + q - b0;  // (below b0: wraps past nb)
+        if (bin < (uint64_t)nb) atomicAdd(&s_bins[((uint32_t)bin << cl) + copy], 1u);
+    };
+    auto count4 = [&](const u32x4 r, uint32_t v) {
+        uint32_t q = (v * 4u) % W;  // (nslots < 2^31: no wrap)
+        count(r.x, q);
+        q = q + 1u == W ? 0u : q + 1u;
+        count(r.y, q);
+        q = q + 1u == W ? 0u : q + 1u;
+        count(r.z, q);
+        q = q + 1u == W ? 0u : q + 1u;
+        count(r.w, q);
+    };
+    const uint32_t nvec = nslots >> 2;
+    const u32x4* r4 = reinterpret_cast<const u32x4*>(rows);
+    const uint32_t step = gridDim.x * (uint32_t)kLoadThreads;
+    uint32_t v = blockIdx.x * (uint32_t)kLoadThreads + tid;
+    for (; v < nvec && nvec - v > 3u * step; v += 4u * step) {  // four 16-B loads in flight a thread
+        const u32x4 a = r4[v], b = r4[v + step], c = r4[v + 2u * step], d = r4[v + 3u * step];
+        count4(a, v);
+        count4(b, v + step);
+        count4(c, v + 2u * step);
+        count4(d, v + 3u * step);
+    }
+    for (; v < nvec; v += step) count4(r4[v], v);
+    if (blockIdx.x == 0 && tid < (nslots & 3u)) {  // the last 1..3 slots
+        const uint32_t s = (nvec << 2) + tid;
+        count(rows[s], s % W);
+    }
+    __syncthreads();
+    for (uint32_t b = tid; b < nb; b += kLoadThreads) {
+        uint32_t sum = 0;
+        for (uint32_t c = 0; c < (1u << cl); c++) sum += s_bins[(b << cl) + ((c + tid) & ((1u << cl) - 1u))];
+        if (sum) atomicAdd(load + b0 + b, (unsigned long long)sum);
+    }
+}
+
+// share[own[i]] += the hash values whose first token >= h is token i (token 0 also takes the
+// values above the last token: lookup's wrap to the smallest token)
+__global__ __launch_bounds__(256) void k_owner_share(RingView rv, unsigned long long* __restrict__ share) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= rv.M) return;
+    const uint64_t t = rv.tok[i];
+    const uint64_t d = i ? t - rv.tok[i - 1] : t + (1ull << 32) - rv.tok[rv.M - 1];
+    if (d) atomicAdd(share + rv.own[i], (unsigned long long)d);
+}
+
+static int load_cus(int device) {
+    int c = 0;
+    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device);
+    return c > 0 ? c : 256;
+}
+
+// Windows past 64 KB of dynamic LDS need the opt-in, on every device that launches the kernels
+// (`device` is the current device: the handle's). A refusal is an error, not a smaller window.
+static void load_lds_opt_in(int device) {
+    static std::mutex mu;
+    static std::vector<uint8_t> done;
+    std::lock_guard<std::mutex> lock(mu);
+    if (device >= 0 && (size_t)device < done.size() && done[device]) return;
+    const int bytes = (int)(kLoadBins * sizeof(uint32_t));
+    RP_HIP(hipFuncSetAttribute((const void*)k_owner_load<0>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    RP_HIP(hipFuncSetAttribute((const void*)k_owner_load<1>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    RP_HIP(hipFuncSetAttribute((const void*)k_owner_load<2>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    RP_HIP(hipFuncSetAttribute((const void*)k_owner_load<3>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    RP_HIP(hipFuncSetAttribute((const void*)k_owner_load<4>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    if (device >= 0) {
+        if ((size_t)device >= done.size()) done.resize((size_t)device + 1, 0);
+        done[device] = 1;
+    }
+}
+
+// Count one chunk's rows (cnt * W slots at ls.rows) into load[0 .. bins), window by window.
+static void launch_owner_load(const uint32_t* rows, uint64_t slots, uint32_t W, uint64_t bins,
+                              unsigned long long* load, int device, hipStream_t st) {
+    load_lds_opt_in(device);
+    RP_REQUIRE(slots < (1ull << 31), "owner_load: chunk too large");
+    // RP_LOAD_BINS: the window (tests reach the multi-window path with it); never past the LDS
+    const uint32_t B = (uint32_t)std::min<uint64_t>(env_pos("RP_LOAD_BINS", kLoadBins), kLoadBins);
+    const bool replicate = !(getenv("RP_LOAD_COPIES") && !strcmp(getenv("RP_LOAD_COPIES"), "0"));  // A/B only
+    const int cus = load_cus(device);
+    for (uint64_t b0 = 0; b0 < bins; b0 += B) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(B, bins - b0);
+        uint32_t cl = 0;
+        if (replicate)
+            while (cl < 6 && ((uint64_t)nb << (cl + 1)) <= B) cl++;
+        const uint32_t words = nb << cl;
+        const unsigned per_cu = words <= kLoadBins2 ? 2u : 1u;
+        const uint64_t nvec = slots / 4;
+        const unsigned g = (unsigned)std::max<uint64_t>(
+            1, std::min<uint64_t>(env_pos("RP_LOAD_GRID", (uint64_t)cus * per_cu), (nvec + kLoadThreads - 1) / kLoadThreads));
+        const size_t lds = (size_t)words * sizeof(uint32_t);
+#define RP_LOADK(WT)                                                                                            \
+    hipLaunchKernelGGL((k_owner_load<WT>), dim3(g), dim3(kLoadThreads), lds, st, rows, (uint32_t)slots, W, b0, \
+                       nb, cl, load)
+        switch (W) {
+            case 1: RP_LOADK(1); break;
+            case 2: RP_LOADK(2); break;
+            case 3: RP_LOADK(3); break;
+            case 4: RP_LOADK(4); break;
+            default: RP_LOADK(0); break;
+        }
+#undef RP_LOADK
+        RP_HIP(hipGetLastError());
+    }
+}
+
+// The chunk walk. look(k0, cnt, rows) queues the lookup of keys [k0, k0 + cnt) into rows on st.
+template <class Look>
+static void owner_load_walk(LoadScratch& ls, uint64_t n, int32_t nrep, uint32_t id_bound, uint32_t id_cap,
+                            bool counts_anything, int accumulate, unsigned long long* load, int device,
+                            hipStream_t st, Look&& look) {
+    RP_REQUIRE(id_cap >= id_bound, "owner_load: id_cap is below the ring's id bound (rp_ring_id_bound)");
+    RP_REQUIRE(id_cap == 0 || load, "owner_load: null load buffer");
+    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const uint64_t bins = (uint64_t)id_cap * W;
+    if (!accumulate && bins) RP_HIP(hipMemsetAsync(load, 0, bins * sizeof(uint64_t), st));
+    if (n == 0 || !counts_anything || bins == 0) return;
+    uint64_t chunk = std::min<uint64_t>(env_pos("RP_LOAD_CHUNK", kLoadChunk), std::max<uint64_t>(1, kLoadSlots / W));
+    chunk = std::min(chunk, n);
+    if (chunk > 4 && chunk < n) chunk &= ~3ull;  // later chunks of 36-byte keys start 16-B aligned when the first does
+    ls.use_on(st);
+    ls.rows.reserve(chunk * W);
+    for (uint64_t k0 = 0; k0 < n; k0 += chunk) {
+        const uint64_t cnt = std::min(chunk, n - k0);
+        look(k0, cnt, ls.rows.p);
+        launch_owner_load(ls.rows.p, cnt * W, W, bins, load, device, st);
+    }
+}
+
+static void owner_load(Ring& r, LoadScratch& ls, const uint8_t* keys, const uint64_t* off, uint32_t stride,
+                       const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t id_cap, int accumulate,
+                       unsigned long long* load, hipStream_t st) {
+    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const int np = (int)std::min<int64_t>(nrep, r.server_count);  // lib/ring/index.js:159-162
+    owner_load_walk(ls, n, nrep, r.nt.size(), id_cap, r.M != 0, accumulate, load, r.device, st,
+                    [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
+                        launch_lookupn(r, hashes ? nullptr : (stride ? keys + k0 * stride : keys),
+                                       (!hashes && !stride) ? off + k0 : nullptr, stride, hashes ? hashes + k0 : nullptr,
+                                       cnt, np, W, rows, nullptr, st);
+                    });
+}
+
+// share[0 .. id_cap) on the host, through the handle's scratch
+static void owner_share(const RingView& rv, LoadScratch& ls, uint32_t id_bound, uint32_t id_cap, uint64_t* share,
+                        hipStream_t st) {
+    RP_REQUIRE(id_cap >= id_bound, "owner_share: id_cap is below the ring's id bound (rp_ring_id_bound)");
+    RP_REQUIRE(id_cap == 0 || share, "owner_share: null share buffer");
+    if (id_cap == 0) return;
+    ls.use_on(st);
+    ls.out.reserve(id_cap);
+    RP_HIP(hipMemsetAsync(ls.out.p, 0, (uint64_t)id_cap * sizeof(uint64_t), st));
+    if (rv.M) {
+        hipLaunchKernelGGL(k_owner_share, dim3(grid_for(rv.M, 256, 1u << 24)), dim3(256), 0, st, rv, ls.out.p);
+        RP_HIP(hipGetLastError());
+    }
+    RP_HIP(hipMemcpyAsync(share, ls.out.p, (uint64_t)id_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    RP_HIP(hipStreamSynchronize(st));
 }
 
 }  // namespace rp
@@ -4102,6 +4310,7 @@ int rp_ring_snapshot(rp_ring* h, rp_ring_snap** out) {
         d.M = r.M;
         d.bbits = r.bbits;
         d.server_count = r.server_count;
+        d.id_bound = r.nt.size();
         d.checksum = r.checksum;
         d.has_checksum = r.has_checksum;
         const uint64_t nbk = (1ull << r.bbits) + 1;
@@ -4237,6 +4446,116 @@ int rp_ring_moved_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_t*
         const rp::Snap& s = S(before);
         RP_REQUIRE(n == 0 || hashes, "moved_hashes: null hash buffer");
         host_moved(r, s, nullptr, nullptr, 0, hashes, n, nrep, cap, idx, before_rows, after_rows, count);
+    });
+}
+
+// ---- owner load and hash-space share
+
+int rp_ring_id_bound(rp_ring* h, uint32_t* out) {
+    return guard_host([&] {
+        rp::Ring& r = R(h);
+        RP_REQUIRE(out, "id_bound: out is null");
+        *out = r.nt.size();
+    });
+}
+
+int rp_ring_owner_load_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_off, uint32_t stride, uint64_t n,
+                           int32_t nrep, uint32_t id_cap, int accumulate, uint64_t* d_load, void* stream) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "owner_load_dev: null key buffer");
+        svc_stop(r);
+        rp::owner_load(r, r.load_ws, d_keys, d_off, stride, nullptr, n, nrep, id_cap, accumulate,
+                       reinterpret_cast<unsigned long long*>(d_load), rp::as_stream(stream));
+    });
+}
+
+// host-buffer forms: keys (or a caller hashFunc's key hashes) in, the counters out
+static void host_owner_load(rp::Ring& r, const char* keys, const uint64_t* off, uint32_t stride,
+                            const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t id_cap, uint64_t* load) {
+    RP_REQUIRE(id_cap >= r.nt.size(), "owner_load: id_cap is below the ring's id bound (rp_ring_id_bound)");
+    RP_REQUIRE(id_cap == 0 || load, "owner_load: null load buffer");
+    svc_stop(r);
+    const uint64_t bins = (uint64_t)id_cap * (nrep > 1 ? (uint64_t)nrep : 1u);
+    if (bins == 0) return;
+    const uint8_t* dk = nullptr;
+    const uint64_t* doff = nullptr;
+    const uint32_t* dh = nullptr;
+    if (n && hashes) {
+        r.io_a.reserve(n);
+        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
+        dh = r.io_a.p;
+    } else if (n) {
+        const uint64_t bytes = stride ? n * stride : off[n];
+        r.io_keys.reserve(bytes + 16);
+        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
+        dk = r.io_keys.p;
+        if (!stride) {
+            r.io_off.reserve(n + 1);
+            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
+            doff = r.io_off.p;
+        }
+    }
+    r.load_ws.use_on(r.st);
+    r.load_ws.out.reserve(bins);
+    rp::owner_load(r, r.load_ws, dk, doff, stride, dh, n, nrep, id_cap, 0, r.load_ws.out.p, r.st);
+    RP_HIP(hipMemcpyAsync(load, r.load_ws.out.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, r.st));
+    RP_HIP(hipStreamSynchronize(r.st));
+}
+
+int rp_ring_owner_load(rp_ring* h, const char* keys, const uint64_t* off, uint32_t stride, uint64_t n, int32_t nrep,
+                       uint32_t id_cap, uint64_t* load) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        RP_REQUIRE(n == 0 || (keys && (stride || off)), "owner_load: null key buffer");
+        host_owner_load(r, keys, off, stride, nullptr, n, nrep, id_cap, load);
+    });
+}
+
+int rp_ring_owner_load_hashes(rp_ring* h, const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t id_cap,
+                              uint64_t* load) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        RP_REQUIRE(n == 0 || hashes, "owner_load_hashes: null hash buffer");
+        host_owner_load(r, nullptr, nullptr, 0, hashes, n, nrep, id_cap, load);
+    });
+}
+
+int rp_ring_snap_owner_load_dev(rp_ring_snap* s, const uint8_t* d_keys, const uint64_t* d_off, uint32_t stride,
+                                uint64_t n, int32_t nrep, uint32_t id_cap, int accumulate, uint64_t* d_load,
+                                void* stream) {
+    return guard([&] {
+        RP_REQUIRE(s, "null snapshot handle");
+        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "snap_owner_load_dev: null key buffer");
+        rp::Snap& d = s->impl;
+        RP_HIP(hipSetDevice(d.device));
+        const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+        const int np = (int)std::min<int64_t>(nrep, d.server_count);  // lib/ring/index.js:159-162
+        hipStream_t st = rp::as_stream(stream);
+        rp::owner_load_walk(d.load_ws, n, nrep, d.id_bound, id_cap, d.M != 0, accumulate,
+                            reinterpret_cast<unsigned long long*>(d_load), d.device, st,
+                            [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
+                                rp::launch_lookupn_view(d.view(), stride ? d_keys + k0 * stride : d_keys,
+                                                        stride ? nullptr : d_off + k0, stride, nullptr, cnt, np, W, rows,
+                                                        nullptr, st);
+                            });
+    });
+}
+
+int rp_ring_owner_share(rp_ring* h, uint32_t id_cap, uint64_t* share) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        svc_stop(r);
+        rp::owner_share(r.view(), r.load_ws, r.nt.size(), id_cap, share, r.st);
+    });
+}
+
+int rp_ring_snap_owner_share(rp_ring_snap* s, uint32_t id_cap, uint64_t* share) {
+    return guard([&] {
+        RP_REQUIRE(s, "null snapshot handle");
+        rp::Snap& d = s->impl;
+        RP_HIP(hipSetDevice(d.device));
+        rp::owner_share(d.view(), d.load_ws, d.id_bound, id_cap, share, nullptr);
     });
 }
 

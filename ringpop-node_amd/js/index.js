@@ -272,6 +272,27 @@ HashRing.prototype.movedNames = function movedNames(keys, moved, n) {
     return out;
 };
 
+// How even is the ring? ownerLoad(keys, n): {server name: [key count per lookupN(key, n) slot]}
+// (slot 0: as primary) for the servers now in the ring, counted on the device without keeping
+// the owner rows; ownerShare(): {server name: how many of the 2^32 hash values it owns} (the
+// expected load; the values sum to 2^32 on a non-empty ring). Counts are Numbers: exact below
+// 2^53.
+HashRing.prototype.ownerLoad = function ownerLoad(keys, n) {
+    n = n === undefined ? 1 : n | 0;
+    var r = native.ringOwnerLoad(this._h, this._customHash ? this._hashes(keys) : keys, n);
+    var w = n > 1 ? n : 1, out = {};
+    for (var i = 0; i < r.names.length; i++) {
+        out[r.names[i]] = Array.prototype.slice.call(r.counts, i * w, i * w + w);
+    }
+    return out;
+};
+
+HashRing.prototype.ownerShare = function ownerShare() {
+    var r = native.ringOwnerShare(this._h), out = {};
+    for (var i = 0; i < r.names.length; i++) { out[r.names[i]] = r.counts[i]; }
+    return out;
+};
+
 // Id-level batch over precomputed key hashes: {owners: Uint32Array(ids, rows of max(n,1)),
 // counts: Uint8Array}; ownerName(id) maps ids back to server names.
 HashRing.prototype.lookupNHashes = function lookupNHashes(hashes, n) {

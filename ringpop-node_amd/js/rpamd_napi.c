@@ -627,6 +627,106 @@ static napi_value js_ring_moved_keys(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* The servers now in the ring (rp_ring_servers order) as {names: [..], counts: Float64Array}:
+ * counts[i * w + q] = table[ids[i] * w + q]. Counts are Numbers: exact below 2^53. */
+static napi_value ring_named_counts(napi_env env, rp_ring *r, const uint64_t *table, size_t w) {
+    uint32_t n = 0;
+    RP_OK(rp_ring_servers(r, NULL, 0, &n));
+    uint32_t *ids = (uint32_t *)malloc(sizeof(uint32_t) * (n ? n : 1));
+    if (!ids) {
+        napi_throw_error(env, NULL, "allocation failed");
+        return NULL;
+    }
+    int rc = rp_ring_servers(r, ids, n, &n);
+    if (rc) {
+        free(ids);
+        RP_OK(rc);
+    }
+    napi_value out, names;
+    void *dc = NULL;
+    napi_value counts = new_typed(env, napi_float64_array, (size_t)n * w, 8, &dc);
+    if (!counts || (!dc && n)) {
+        free(ids);
+        napi_throw_error(env, NULL, "allocation failed");
+        return NULL;
+    }
+    napi_create_array_with_length(env, n, &names);
+    for (uint32_t i = 0; i < n; i++) {
+        napi_set_element(env, names, i, ring_name(env, r, ids[i]));
+        for (size_t q = 0; q < w; q++) ((double *)dc)[i * w + q] = (double)table[(size_t)ids[i] * w + q];
+    }
+    free(ids);
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "names", names);
+    napi_set_named_property(env, out, "counts", counts);
+    return out;
+}
+
+/* ringOwnerLoad(h, keys[] | Uint32Array hashes, n) -> {names, counts: Float64Array}: for each
+ * server now in the ring, how many keys have it in slot q of their lookupN(key, n) row
+ * (rp_ring_owner_load / _hashes), max(n,1) counts a server. */
+static napi_value js_ring_owner_load(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    handle_t *h = get_handle(env, argv[0], 1);
+    if (!h) return NULL;
+    rp_ring *r = (rp_ring *)h->p;
+    int32_t nrep = 0;
+    NAPI_OK(napi_get_value_int32(env, argv[2], &nrep));
+    bool is_typed = false;
+    napi_is_typedarray(env, argv[1], &is_typed);
+    size_t n = 0;
+    void *hv = NULL;
+    strpack_t keys;
+    memset(&keys, 0, sizeof(keys));
+    if (is_typed) {
+        if (typed_get(env, argv[1], napi_uint32_array, &hv, &n)) {
+            napi_throw_type_error(env, NULL, "hashes must be a Uint32Array");
+            return NULL;
+        }
+    } else {
+        if (strpack_from_array(env, argv[1], &keys)) return NULL;
+        n = keys.n;
+    }
+    const size_t w = nrep > 1 ? (size_t)nrep : 1u;
+    uint32_t cap = 0;
+    int rc = rp_ring_id_bound(r, &cap);
+    uint64_t *load = rc ? NULL : (uint64_t *)calloc((size_t)cap * w + 1, 8);
+    if (!rc && !load) {
+        if (!is_typed) strpack_free(&keys);
+        napi_throw_error(env, NULL, "allocation failed");
+        return NULL;
+    }
+    if (!rc)
+        rc = is_typed ? rp_ring_owner_load_hashes(r, (const uint32_t *)hv, n, nrep, cap, load)
+                      : rp_ring_owner_load(r, keys.bytes, keys.off64, 0, n, nrep, cap, load);
+    if (!is_typed) strpack_free(&keys);
+    napi_value out = rc ? NULL : ring_named_counts(env, r, load, w);
+    free(load);
+    RP_OK(rc);
+    return out;
+}
+
+/* ringOwnerShare(h) -> {names, counts: Float64Array}: how many of the 2^32 hash values each
+ * server now in the ring owns (rp_ring_owner_share). */
+static napi_value js_ring_owner_share(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    handle_t *h = get_handle(env, argv[0], 1);
+    if (!h) return NULL;
+    rp_ring *r = (rp_ring *)h->p;
+    uint32_t cap = 0;
+    int rc = rp_ring_id_bound(r, &cap);
+    uint64_t *share = rc ? NULL : (uint64_t *)calloc((size_t)cap + 1, 8);
+    if (!rc && !share) {
+        napi_throw_error(env, NULL, "allocation failed");
+        return NULL;
+    }
+    if (!rc) rc = rp_ring_owner_share(r, cap, share);
+    napi_value out = rc ? NULL : ring_named_counts(env, r, share, 1);
+    free(share);
+    RP_OK(rc);
+    return out;
+}
+
 /* lookupNBatch(h, keys[], n) -> arrays of names, lookupN() of every key (:157-189). */
 static napi_value js_ring_lookupn(napi_env env, napi_callback_info info) {
     ARGS(3);
@@ -1359,6 +1459,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringSnapshot", NULL, js_ring_snapshot, NULL, NULL, NULL, napi_default, NULL},
         {"ringSnapInfo", NULL, js_ring_snap_info, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedKeys", NULL, js_ring_moved_keys, NULL, NULL, NULL, napi_default, NULL},
+        {"ringOwnerLoad", NULL, js_ring_owner_load, NULL, NULL, NULL, napi_default, NULL},
+        {"ringOwnerShare", NULL, js_ring_owner_share, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later);
     return exports;
