@@ -233,6 +233,46 @@ int rp_ring_snap_owner_load_dev(rp_ring_snap *s, const uint8_t *d_keys, const ui
 int rp_ring_owner_share(rp_ring *r, uint32_t id_cap, uint64_t *share);
 int rp_ring_snap_owner_share(rp_ring_snap *s, uint32_t id_cap, uint64_t *share);
 
+/* Moved ranges: which hash intervals changed hands between a snapshot and the ring now, without
+ * any key (range hand-off of stores indexed by hash; planning a ring change before keys exist).
+ * For a hash h, row_S(h) is the row rp_ring_lookupn_hashes writes for h under ring state S with
+ * nrep: W = max(nrep, 1) slots padded with RP_NULL_ID (nrep <= 0 keeps lookupn's single-step
+ * form, so a hash above the last token then has an empty row). The moved set is
+ * {h in [0, 2^32) : row_before(h) != row_after(h)}. The result is its unique decomposition into
+ * maximal runs of consecutive hash values on which the pair (row_before, row_after) is constant,
+ * ascending by lo. Runs do not wrap: a run that ends at 2^32-1 and one that starts at 0 are two
+ * entries even when their rows are equal.
+ *   lo[j], hi[j]              the run, both ends inclusive
+ *   before_rows / after_rows  [j*W .. j*W+W): the two rows of run j; either may be NULL
+ *   *count                    the number of runs, counted in full
+ *   *moved_hashes             the size of the moved set, counted in full (it can be 2^32)
+ * Nothing at or past entry cap is touched (cap = 0: the counts only; the arrays may then be NULL).
+ * count is at most tokens_before + tokens_now + 1: both rows are constant between neighbours of
+ * the sorted union of both token sets with 2^32-1 appended, so a cap of that size holds every run.
+ * `before` must be a snapshot of a ring on r's device with r's id space (normally of r itself), as
+ * for rp_ring_moved_keys. nrep > 8 (rows are compared in registers), a null handle and a snapshot
+ * on another device return RP_EINVAL with nothing written.
+ * The _dev forms take device buffers (d_count one uint32, d_moved_hashes one uint64, 8-byte
+ * aligned), are stream-ordered and never sync with the host, except that a stream other than the
+ * ring's own first waits for the ring's pending rebuilds (as rp_ring_moved_keys_dev does). Their
+ * scratch (13 bytes per token of either side) belongs to the handle and is allocated when it
+ * first grows, never per call after that. */
+int rp_ring_moved_ranges_dev(rp_ring *r, const rp_ring_snap *before, int32_t nrep, uint32_t cap,
+                             uint32_t *d_lo, uint32_t *d_hi, uint32_t *d_before, uint32_t *d_after,
+                             uint32_t *d_count, uint64_t *d_moved_hashes, void *stream);
+int rp_ring_moved_ranges(rp_ring *r, const rp_ring_snap *before, int32_t nrep, uint32_t cap,
+                         uint32_t *lo, uint32_t *hi, uint32_t *before_rows, uint32_t *after_rows,
+                         uint32_t *count, uint64_t *moved_hashes);
+/* The same between two snapshots of one ring (after owns the scratch, allocated at first use). */
+int rp_ring_snap_moved_ranges_dev(const rp_ring_snap *before, rp_ring_snap *after, int32_t nrep, uint32_t cap,
+                                  uint32_t *d_lo, uint32_t *d_hi, uint32_t *d_before, uint32_t *d_after,
+                                  uint32_t *d_count, uint64_t *d_moved_hashes, void *stream);
+int rp_ring_snap_moved_ranges(const rp_ring_snap *before, rp_ring_snap *after, int32_t nrep, uint32_t cap,
+                              uint32_t *lo, uint32_t *hi, uint32_t *before_rows, uint32_t *after_rows,
+                              uint32_t *count, uint64_t *moved_hashes);
+/* The snapshot's sorted (token, owner) arrays, as rp_ring_dump gives them for a ring. */
+int rp_ring_snap_dump(const rp_ring_snap *s, uint32_t *tokens, uint32_t *owners, uint32_t cap);
+
 /* ------------------------------------------------------------------ Membership
  * Replaces the hot path of lib/membership/index.js Membership: update (249-324) with the
  * Member.evaluateUpdate rules (lib/membership/member.js:71-202) and computeChecksum /

@@ -85,6 +85,11 @@ SIGNATURES = {
     "rp_ring_snap_owner_load_dev": (_INT, [_P, _P, _P, _U32, _U64, _I32, _U32, _INT, _P, _P]),
     "rp_ring_owner_share": (_INT, [_P, _U32, _P]),
     "rp_ring_snap_owner_share": (_INT, [_P, _U32, _P]),
+    "rp_ring_moved_ranges_dev": (_INT, [_P, _P, _I32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_moved_ranges": (_INT, [_P, _P, _I32, _U32, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_snap_moved_ranges_dev": (_INT, [_P, _P, _I32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_snap_moved_ranges": (_INT, [_P, _P, _I32, _U32, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_snap_dump": (_INT, [_P, _P, _P, _U32]),
     "rp_members_create": (_INT, [_U32, _INT, _P]),
     "rp_members_destroy": (_INT, [_P]),
     "rp_members_intern": (_INT, [_P, _P, _P, _U32, _P]),
@@ -591,6 +596,38 @@ class HashRing:
         share = self.owner_share_ids()
         return {s: int(share[self.server_id(s)]) for s in self._servers}
 
+    # -- moved ranges (range hand-off, and planning a change before any key exists)
+    def moved_range_ids(self, before, n=1, cap=None):
+        """(lo, hi, before_rows, after_rows): the hash intervals [lo, hi] (inclusive, ascending)
+        on which the lookupN(h, n) row under the snapshot `before` differs from the row now, as
+        maximal runs of one (row before, row now) pair, with the two rows [m, max(n,1)] (NULL_ID
+        padded). Nothing is hashed, so a ring with a caller hashFunc works as any other. cap bounds
+        the entries returned (default: tokens before + tokens now + 1, which holds every run);
+        `moved_range_count` and `moved_hash_count` hold the full counts."""
+        bound = before.info()["tokens"] + self.size + 1
+        return _moved_ranges(self, lib().rp_ring_moved_ranges, (self._h, before._h), n, cap, bound)
+
+    def movedRanges(self, before, n=1):
+        """[(lo, hi, [owner names before], [owner names now])], ascending."""
+        lo, hi, br, ar = self.moved_range_ids(before, n)
+        return [(int(l), int(h), [self.name(x) for x in b if x != NULL_ID], [self.name(x) for x in a if x != NULL_ID])
+                for l, h, b, a in zip(lo, hi, br, ar)]
+
+    def movedShare(self, before):
+        """{(owner name before or None, owner name now or None): hash values}: how much of the
+        hash space moved from whom to whom (lookup, n = 1); the values sum to moved_hash_count."""
+        lo, hi, br, ar = self.moved_range_ids(before, 1)
+        out = {}
+        for l, h, b, a in zip(lo, hi, br[:, 0], ar[:, 0]):
+            k = (self.name(b), self.name(a))
+            out[k] = out.get(k, 0) + int(h) - int(l) + 1
+        return out
+
+    def moved_ranges_dev(self, before, nrep, cap, lo_ptr, hi_ptr, before_ptr, after_ptr, count_ptr, moved_hashes_ptr,
+                         stream=None):
+        check(lib().rp_ring_moved_ranges_dev(self._h, before._h, nrep, cap, lo_ptr, hi_ptr, before_ptr, after_ptr,
+                                             count_ptr, moved_hashes_ptr, stream))
+
     # -- device-resident hot path (pointers from torch tensors / hipMalloc)
     def lookupn_dev(self, keys_ptr, n, nrep, owners_ptr, counts_ptr=None, stride=36, off_ptr=None, stream=None):
         check(lib().rp_ring_lookupn_dev(self._h, keys_ptr, off_ptr, stride, n, nrep, owners_ptr, counts_ptr, stream))
@@ -646,6 +683,42 @@ class RingSnapshot:
         out = np.zeros(cap, dtype=np.uint64)
         check(lib().rp_ring_snap_owner_share(self._h, cap, out.ctypes.data if cap else None))
         return out
+
+    def moved_range_ids(self, after, n=1, cap=None):
+        """HashRing.moved_range_ids between this snapshot and the later snapshot `after` of the
+        same ring (the full counts are left on this snapshot)."""
+        bound = self.info()["tokens"] + after.info()["tokens"] + 1
+        return _moved_ranges(self, lib().rp_ring_snap_moved_ranges, (self._h, after._h), n, cap, bound)
+
+    def moved_ranges_dev(self, after, nrep, cap, lo_ptr, hi_ptr, before_ptr, after_ptr, count_ptr, moved_hashes_ptr,
+                         stream=None):
+        check(lib().rp_ring_snap_moved_ranges_dev(self._h, after._h, nrep, cap, lo_ptr, hi_ptr, before_ptr, after_ptr,
+                                                  count_ptr, moved_hashes_ptr, stream))
+
+    def dump(self):
+        """The snapshot's sorted (tokens, owners), as HashRing.dump gives them for the ring."""
+        m = self.info()["tokens"]
+        t = np.empty(max(m, 1), dtype=np.uint32)
+        o = np.empty(max(m, 1), dtype=np.uint32)
+        check(lib().rp_ring_snap_dump(self._h, t.ctypes.data, o.ctypes.data, m))
+        return t[:m], o[:m]
+
+
+def _moved_ranges(holder, fn, handles, n, cap, bound):
+    """The host moved-ranges call `fn` on its two handles; the full counts go to `holder`."""
+    w = max(int(n), 1)
+    c = bound if cap is None else min(int(cap), bound)
+    lo = np.empty(max(c, 1), dtype=np.uint32)
+    hi = np.empty(max(c, 1), dtype=np.uint32)
+    br = np.empty((max(c, 1), w), dtype=np.uint32)
+    ar = np.empty((max(c, 1), w), dtype=np.uint32)
+    cnt, mh = ctypes.c_uint32(), ctypes.c_uint64()
+    check(fn(handles[0], handles[1], int(n), c, lo.ctypes.data, hi.ctypes.data, br.ctypes.data, ar.ctypes.data,
+             ctypes.byref(cnt), ctypes.byref(mh)))
+    holder.moved_range_count = cnt.value
+    holder.moved_hash_count = mh.value
+    m = min(cnt.value, c)
+    return lo[:m], hi[:m], br[:m], ar[:m]
 
 
 class DampConfig(ctypes.Structure):

@@ -2441,6 +2441,17 @@ struct LoadScratch {
     void use_on(hipStream_t st) { order.use_on(st); }
 };
 
+// The scratch of the moved-ranges calls of one handle (the ring now, or the `after` snapshot),
+// ordered across streams in the same way.
+struct RangeScratch {
+    DevBuf<uint32_t> val, mi, mj;  // the merged tokens and their first-token positions in both rings
+    DevBuf<uint32_t> tot;          // heads per tile, then their exclusive scan
+    DevBuf<uint8_t> flg;           // per merged element: kRngHead | kRngTailPrev | kRngFinal
+    DevBuf<uint32_t> io;           // the host forms' outputs
+    StreamOrder order;
+    void use_on(hipStream_t st) { order.use_on(st); }
+};
+
 struct Ring {
     int device = 0;
     hipStream_t st = nullptr;
@@ -2507,6 +2518,7 @@ struct Ring {
     DevBuf<uint32_t> grp_own, grp_key, grp_first, grp_dk, grp_dv, grp_rank;
     Scratch ws;
     LoadScratch load_ws;  // owner load / share
+    RangeScratch range_ws;  // moved ranges
 
     RingView view() const {
         return RingView{tok.p, own.p, bstart.p, M, 32u - bbits};
@@ -3234,6 +3246,7 @@ struct Snap {
     uint32_t id_bound = 0;  // the ring's interned ids at snapshot time (the owner-load id_cap check)
     bool has_checksum = false;
     LoadScratch load_ws;  // owner load / share (allocated at first use)
+    RangeScratch range_ws;  // moved ranges, when this snapshot is the `after` side (allocated at first use)
     RingView view() const { return RingView{tok.p, own.p, bstart.p, M, 32u - bbits}; }
 };
 
@@ -3683,6 +3696,261 @@ static void owner_share(const RingView& rv, LoadScratch& ls, uint32_t id_bound, 
     }
     RP_HIP(hipMemcpyAsync(share, ls.out.p, (uint64_t)id_cap * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     RP_HIP(hipStreamSynchronize(st));
+}
+
+// ------------------------------------------------------------- moved ranges
+// Which hash intervals changed hands between two ring states, without any key. lookupN depends on
+// the hash only through "the first token >= h", so on every interval (u[k-1], u[k]] of the sorted
+// union u of both rings' tokens (2^32-1 appended) both rows are constant: at most Mb + Ma + 1
+// intervals can differ. Four launches, none of which waits on another workgroup:
+//   k_ranges_merge  one thread per token of either ring (and one for the appended 2^32-1): its
+//                   first-token positions (i, j) in both rings by bucket search, and its slot in
+//                   the stable merge (before's tokens first among equals), where (u, i, j) go.
+//                   (i, j) are lower bounds by value, so equal tokens carry equal positions.
+//   k_ranges_flag   one thread per merged element k. An element whose value equals its
+//                   predecessor's closes an empty interval and is skipped. Otherwise both rows are
+//                   walked from (i, j) of k and of k - 1 (k - 1 carries the previous distinct
+//                   value, whose interval ends where k's begins) and compared in registers:
+//                   head = moved and not a continuation of k - 1's pair; tail-of-previous = k - 1
+//                   moved and k does not continue it. The last element flags the final tail. Heads
+//                   are counted per tile; the moved hash values are summed in full.
+//   k_ranges_scan   exclusive scan of the tile totals (one workgroup, in passes with a carry).
+//   k_ranges_write  heads write lo and both rows at their rank; tails write hi at (heads before
+//                   them) - 1; the last element writes the count.
+// Tests shrink the tile (RP_RANGES_TILE, elements a workgroup) and the scan pass (RP_RANGES_SCAN)
+// so that several tiles and several scan passes run on a few thousand tokens.
+constexpr int kRngThreads = 256;
+constexpr int kRngScanThreads = 1024;
+constexpr uint32_t kRngHead = 1u, kRngTailPrev = 2u, kRngFinal = 4u;
+
+__global__ __launch_bounds__(kRngThreads) void k_ranges_merge(RingView bv, RingView av, uint32_t* __restrict__ val,
+                                                              uint32_t* __restrict__ mi, uint32_t* __restrict__ mj) {
+    const uint32_t N = bv.M + av.M;
+    const uint32_t g = blockIdx.x * (uint32_t)kRngThreads + threadIdx.x;
+    if (g > N) return;
+    const uint32_t t = g < bv.M ? bv.tok[g] : (g < N ? av.tok[g - bv.M] : NIL);
+    const uint32_t i = moved_find(bv, t), j = moved_find(av, t);
+    uint32_t pos = N;
+    if (g < bv.M) pos = g + j;  // + after's tokens below t
+    else if (g < N) pos = (g - bv.M) + (t == NIL ? bv.M : moved_find(bv, t + 1u));  // + before's tokens <= t
+    if (pos > N) return;  // (sorted arrays never get here; an unsorted one must not write out of bounds)
+    val[pos] = t;
+    mi[pos] = i;
+    mj[pos] = j;
+}
+
+// both rows from the first-token positions (i, j); true when they differ
+template <int MAXN>
+__device__ __forceinline__ bool ranges_rows(const RingView& bv, int npb, const RingView& av, int npa, uint32_t i,
+                                            uint32_t j, uint32_t (&rb)[MAXN], uint32_t (&ra)[MAXN]) {
+    moved_walk<MAXN>(bv, i < bv.M ? i : bv.M, npb, rb);
+    moved_walk<MAXN>(av, j < av.M ? j : av.M, npa, ra);
+    bool d = false;
+#pragma unroll
+    for (int q = 0; q < MAXN; q++) d |= rb[q] != ra[q];
+    return d;
+}
+
+template <int MAXN>
+__global__ __launch_bounds__(kRngThreads) void k_ranges_flag(RingView bv, int npb, RingView av, int npa,
+                                                             const uint32_t* __restrict__ val,
+                                                             const uint32_t* __restrict__ mi,
+                                                             const uint32_t* __restrict__ mj, uint32_t tile_n,
+                                                             uint8_t* __restrict__ flg, uint32_t* __restrict__ tot,
+                                                             unsigned long long* __restrict__ moved_hashes) {
+    __shared__ uint32_t s_heads;
+    __shared__ unsigned long long s_moved;
+    const uint32_t N = bv.M + av.M, tid = threadIdx.x;
+    const uint32_t k = blockIdx.x * tile_n + tid;
+    if (tid == 0) {
+        s_heads = 0;
+        s_moved = 0;
+    }
+    __syncthreads();
+    uint32_t f = 0;
+    if (tid < tile_n && k <= N) {
+        const uint32_t u = val[k], up = k ? val[k - 1] : 0u;
+        const bool rep = k == 0 || u != up, fin = k == N;
+        if (rep || fin) {
+            uint32_t rb[MAXN], ra[MAXN];
+            const bool moved = ranges_rows<MAXN>(bv, npb, av, npa, mi[k], mj[k], rb, ra);
+            bool prev_moved = false, cont = false;
+            if (rep && k > 0) {
+                uint32_t pb[MAXN], pa[MAXN];
+                prev_moved = ranges_rows<MAXN>(bv, npb, av, npa, mi[k - 1], mj[k - 1], pb, pa);
+                bool same = true;
+#pragma unroll
+                for (int q = 0; q < MAXN; q++) same &= (pb[q] == rb[q]) & (pa[q] == ra[q]);
+                cont = prev_moved & moved & same;
+            }
+            if (rep && moved && !cont) f |= kRngHead;
+            if (rep && prev_moved && !cont) f |= kRngTailPrev;
+            if (fin && moved) f |= kRngFinal;
+            if (rep && moved) atomicAdd(&s_moved, k ? (unsigned long long)(u - up) : (unsigned long long)u + 1ull);
+        }
+        flg[k] = (uint8_t)f;
+    }
+    const uint64_t m = __ballot(f & kRngHead);
+    if ((tid & 63u) == 0 && m) atomicAdd(&s_heads, (uint32_t)__popcll(m));
+    __syncthreads();
+    if (tid == 0) {
+        tot[blockIdx.x] = s_heads;
+        if (s_moved) atomicAdd(moved_hashes, s_moved);
+    }
+}
+
+__global__ __launch_bounds__(kRngScanThreads) void k_ranges_scan(uint32_t* __restrict__ tot, uint32_t ntiles,
+                                                                 uint32_t pass) {
+    __shared__ uint32_t s_w[kRngScanThreads / 64];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < ntiles; base += pass) {
+        const bool in = tid < pass && tid < ntiles - base;
+        const uint32_t x = in ? tot[base + tid] : 0u;
+        uint32_t inc = x;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t y = __shfl_up(inc, d);
+            if (lane >= (uint32_t)d) inc += y;
+        }
+        if (lane == 63) s_w[wave] = inc;
+        __syncthreads();
+        uint32_t wpre = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kRngScanThreads / 64; w++) {
+            const uint32_t c = s_w[w];
+            wpre += (uint32_t)w < wave ? c : 0u;
+            total += c;
+        }
+        if (in) tot[base + tid] = carry + wpre + inc - x;
+        carry += total;
+        __syncthreads();
+    }
+}
+
+template <int MAXN>
+__global__ __launch_bounds__(kRngThreads) void k_ranges_write(RingView bv, int npb, RingView av, int npa,
+                                                              const uint32_t* __restrict__ val,
+                                                              const uint32_t* __restrict__ mi,
+                                                              const uint32_t* __restrict__ mj,
+                                                              const uint8_t* __restrict__ flg,
+                                                              const uint32_t* __restrict__ off, uint32_t tile_n,
+                                                              uint32_t W, uint32_t cap, uint32_t* __restrict__ lo,
+                                                              uint32_t* __restrict__ hi, uint32_t* __restrict__ brow,
+                                                              uint32_t* __restrict__ arow, uint32_t* __restrict__ count) {
+    __shared__ uint32_t s_w[kRngThreads / 64];
+    const uint32_t N = bv.M + av.M, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t k = blockIdx.x * tile_n + tid;
+    const bool active = tid < tile_n && k <= N;
+    const uint32_t f = active ? flg[k] : 0u;
+    const bool head = f & kRngHead;
+    const uint64_t m = __ballot(head);
+    if (lane == 0) s_w[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    uint32_t excl = off[blockIdx.x] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int w = 0; w < kRngThreads / 64; w++) excl += (uint32_t)w < wave ? s_w[w] : 0u;
+    // excl = heads before this element; every write is bounded by cap
+    if ((f & kRngTailPrev) && excl > 0 && excl - 1u < cap) hi[excl - 1u] = val[k - 1];
+    if (head && excl < cap) {
+        lo[excl] = k ? val[k - 1] + 1u : 0u;
+        if (brow || arow) {
+            uint32_t rb[MAXN], ra[MAXN];
+            ranges_rows<MAXN>(bv, npb, av, npa, mi[k], mj[k], rb, ra);
+#pragma unroll
+            for (int q = 0; q < MAXN; q++) {
+                if ((uint32_t)q < W) {
+                    if (brow) brow[(uint64_t)excl * W + q] = rb[q];
+                    if (arow) arow[(uint64_t)excl * W + q] = ra[q];
+                }
+            }
+        }
+    }
+    if (active && k == N) {
+        const uint32_t total = excl + (head ? 1u : 0u);
+        if ((f & kRngFinal) && total > 0 && total - 1u < cap) hi[total - 1u] = NIL;  // the run that ends at 2^32-1
+        *count = total;
+    }
+}
+
+// Ranges between the states (bv, sc_b servers) and (av, sc_a servers); outputs as
+// rp_ring_moved_ranges_dev documents. Everything is queued on st.
+static void moved_ranges(const RingView& bv, uint32_t sc_b, const RingView& av, uint32_t sc_a, RangeScratch& ws,
+                         int32_t nrep, uint32_t cap, uint32_t* lo, uint32_t* hi, uint32_t* brow, uint32_t* arow,
+                         uint32_t* count, uint64_t* moved_hashes, hipStream_t st) {
+    RP_REQUIRE(nrep <= 8, "moved_ranges: nrep is at most 8 (the rows are compared in registers)");
+    RP_REQUIRE(count && moved_hashes, "moved_ranges: null count");
+    RP_REQUIRE(cap == 0 || (lo && hi), "moved_ranges: null range buffer");
+    RP_REQUIRE((uint64_t)bv.M + av.M < (1ull << 31), "moved_ranges: more than 2^31 tokens");
+    RP_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+    RP_HIP(hipMemsetAsync(moved_hashes, 0, sizeof(uint64_t), st));
+    if (bv.M == 0 && av.M == 0) return;
+    const uint32_t n = bv.M + av.M + 1u;  // merged elements
+    const uint32_t tile_n = (uint32_t)std::min<uint64_t>(env_pos("RP_RANGES_TILE", kRngThreads), kRngThreads);
+    const uint32_t pass = (uint32_t)std::min<uint64_t>(env_pos("RP_RANGES_SCAN", kRngScanThreads), kRngScanThreads);
+    const uint32_t ntiles = (n + tile_n - 1u) / tile_n;
+    ws.use_on(st);
+    ws.val.reserve(n);
+    ws.mi.reserve(n);
+    ws.mj.reserve(n);
+    ws.flg.reserve(n);
+    ws.tot.reserve(ntiles);
+    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const int npb = (int)std::min<int64_t>(nrep, sc_b), npa = (int)std::min<int64_t>(nrep, sc_a);
+    hipLaunchKernelGGL(k_ranges_merge, dim3((n + kRngThreads - 1) / kRngThreads), dim3(kRngThreads), 0, st, bv, av,
+                       ws.val.p, ws.mi.p, ws.mj.p);
+    RP_HIP(hipGetLastError());
+    unsigned long long* mh = reinterpret_cast<unsigned long long*>(moved_hashes);
+#define RP_RANGES(MAXN)                                                                                              \
+    do {                                                                                                             \
+        hipLaunchKernelGGL((k_ranges_flag<MAXN>), dim3(ntiles), dim3(kRngThreads), 0, st, bv, npb, av, npa,          \
+                           ws.val.p, ws.mi.p, ws.mj.p, tile_n, ws.flg.p, ws.tot.p, mh);                              \
+        RP_HIP(hipGetLastError());                                                                                   \
+        hipLaunchKernelGGL(k_ranges_scan, dim3(1), dim3(kRngScanThreads), 0, st, ws.tot.p, ntiles, pass);            \
+        RP_HIP(hipGetLastError());                                                                                   \
+        hipLaunchKernelGGL((k_ranges_write<MAXN>), dim3(ntiles), dim3(kRngThreads), 0, st, bv, npb, av, npa,         \
+                           ws.val.p, ws.mi.p, ws.mj.p, ws.flg.p, ws.tot.p, tile_n, W, cap, lo, hi, brow, arow,       \
+                           count);                                                                                   \
+        RP_HIP(hipGetLastError());                                                                                   \
+    } while (0)
+    if (W == 1) RP_RANGES(1);
+    else if (W <= 4) RP_RANGES(4);
+    else RP_RANGES(8);
+#undef RP_RANGES
+}
+
+// The host form: the same through the handle's scratch, then two copies (the counts, then the
+// entries that exist).
+static void host_moved_ranges(const RingView& bv, uint32_t sc_b, const RingView& av, uint32_t sc_a, RangeScratch& ws,
+                              int32_t nrep, uint32_t cap, uint32_t* lo, uint32_t* hi, uint32_t* brows, uint32_t* arows,
+                              uint32_t* count, uint64_t* moved_hashes, hipStream_t st) {
+    RP_REQUIRE(nrep <= 8, "moved_ranges: nrep is at most 8 (the rows are compared in registers)");
+    RP_REQUIRE(count && moved_hashes, "moved_ranges: null count");
+    RP_REQUIRE(cap == 0 || (lo && hi), "moved_ranges: null range buffer");
+    RP_REQUIRE((uint64_t)bv.M + av.M < (1ull << 31), "moved_ranges: more than 2^31 tokens");
+    // io = [moved_hashes 2 | count 1 | pad 1 | lo c | hi c | before rows c*W | after rows c*W]
+    const uint64_t c = std::min<uint64_t>(cap, (uint64_t)bv.M + av.M + 1u), W = nrep > 1 ? (uint64_t)nrep : 1u;
+    ws.use_on(st);
+    ws.io.reserve(4 + c * (2 + 2 * W));
+    uint32_t* dlo = ws.io.p + 4;
+    uint32_t* dhi = dlo + c;
+    uint32_t* dbr = dhi + c;
+    uint32_t* dar = dbr + c * W;
+    moved_ranges(bv, sc_b, av, sc_a, ws, nrep, (uint32_t)c, c ? dlo : nullptr, c ? dhi : nullptr,
+                 brows ? dbr : nullptr, arows ? dar : nullptr, ws.io.p + 2, reinterpret_cast<uint64_t*>(ws.io.p), st);
+    uint32_t head[4] = {0, 0, 0, 0};
+    RP_HIP(hipMemcpyAsync(head, ws.io.p, sizeof(head), hipMemcpyDeviceToHost, st));
+    RP_HIP(hipStreamSynchronize(st));
+    *count = head[2];
+    *moved_hashes = (uint64_t)head[0] | ((uint64_t)head[1] << 32);
+    const uint64_t m = std::min<uint64_t>(head[2], c);
+    if (m) {
+        RP_HIP(hipMemcpyAsync(lo, dlo, m * 4, hipMemcpyDeviceToHost, st));
+        RP_HIP(hipMemcpyAsync(hi, dhi, m * 4, hipMemcpyDeviceToHost, st));
+        if (brows) RP_HIP(hipMemcpyAsync(brows, dbr, m * W * 4, hipMemcpyDeviceToHost, st));
+        if (arows) RP_HIP(hipMemcpyAsync(arows, dar, m * W * 4, hipMemcpyDeviceToHost, st));
+        RP_HIP(hipStreamSynchronize(st));
+    }
 }
 
 }  // namespace rp
@@ -4556,6 +4824,77 @@ int rp_ring_snap_owner_share(rp_ring_snap* s, uint32_t id_cap, uint64_t* share) 
         rp::Snap& d = s->impl;
         RP_HIP(hipSetDevice(d.device));
         rp::owner_share(d.view(), d.load_ws, d.id_bound, id_cap, share, nullptr);
+    });
+}
+
+// ---- moved ranges
+
+int rp_ring_moved_ranges_dev(rp_ring* h, const rp_ring_snap* before, int32_t nrep, uint32_t cap, uint32_t* d_lo,
+                             uint32_t* d_hi, uint32_t* d_before, uint32_t* d_after, uint32_t* d_count,
+                             uint64_t* d_moved_hashes, void* stream) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(s.device == r.device, "moved_ranges: the snapshot lives on another device");
+        svc_stop(r);
+        hipStream_t st = rp::as_stream(stream);
+        // the ring is rebuilt on r.st; make the caller's stream wait for it
+        if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
+        rp::moved_ranges(s.view(), s.server_count, r.view(), r.server_count, r.range_ws, nrep, cap, d_lo, d_hi,
+                         d_before, d_after, d_count, d_moved_hashes, st);
+    });
+}
+
+int rp_ring_moved_ranges(rp_ring* h, const rp_ring_snap* before, int32_t nrep, uint32_t cap, uint32_t* lo,
+                         uint32_t* hi, uint32_t* before_rows, uint32_t* after_rows, uint32_t* count,
+                         uint64_t* moved_hashes) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(s.device == r.device, "moved_ranges: the snapshot lives on another device");
+        svc_stop(r);
+        rp::host_moved_ranges(s.view(), s.server_count, r.view(), r.server_count, r.range_ws, nrep, cap, lo, hi,
+                              before_rows, after_rows, count, moved_hashes, r.st);
+    });
+}
+
+int rp_ring_snap_moved_ranges_dev(const rp_ring_snap* before, rp_ring_snap* after, int32_t nrep, uint32_t cap,
+                                  uint32_t* d_lo, uint32_t* d_hi, uint32_t* d_before, uint32_t* d_after,
+                                  uint32_t* d_count, uint64_t* d_moved_hashes, void* stream) {
+    return guard([&] {
+        const rp::Snap& b = S(before);
+        RP_REQUIRE(after, "null snapshot handle");
+        rp::Snap& a = after->impl;
+        RP_REQUIRE(b.device == a.device, "moved_ranges: the snapshots live on different devices");
+        RP_HIP(hipSetDevice(a.device));
+        rp::moved_ranges(b.view(), b.server_count, a.view(), a.server_count, a.range_ws, nrep, cap, d_lo, d_hi,
+                         d_before, d_after, d_count, d_moved_hashes, rp::as_stream(stream));
+    });
+}
+
+int rp_ring_snap_moved_ranges(const rp_ring_snap* before, rp_ring_snap* after, int32_t nrep, uint32_t cap,
+                              uint32_t* lo, uint32_t* hi, uint32_t* before_rows, uint32_t* after_rows,
+                              uint32_t* count, uint64_t* moved_hashes) {
+    return guard([&] {
+        const rp::Snap& b = S(before);
+        RP_REQUIRE(after, "null snapshot handle");
+        rp::Snap& a = after->impl;
+        RP_REQUIRE(b.device == a.device, "moved_ranges: the snapshots live on different devices");
+        RP_HIP(hipSetDevice(a.device));
+        rp::host_moved_ranges(b.view(), b.server_count, a.view(), a.server_count, a.range_ws, nrep, cap, lo, hi,
+                              before_rows, after_rows, count, moved_hashes, nullptr);
+    });
+}
+
+int rp_ring_snap_dump(const rp_ring_snap* s, uint32_t* tokens, uint32_t* owners, uint32_t cap) {
+    return guard([&] {
+        const rp::Snap& d = S(s);
+        RP_HIP(hipSetDevice(d.device));
+        const uint32_t n = std::min(cap, d.M);
+        if (n) {
+            if (tokens) RP_HIP(hipMemcpy(tokens, d.tok.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+            if (owners) RP_HIP(hipMemcpy(owners, d.own.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        }
     });
 }
 

@@ -272,6 +272,33 @@ HashRing.prototype.movedNames = function movedNames(keys, moved, n) {
     return out;
 };
 
+// Range hand-off, and planning a change before any key exists: movedRanges(snap, n) gives the hash
+// intervals [lo, hi] (inclusive, ascending, maximal runs of one pair of rows) on which lookupN(h, n)
+// differs between the snapshot and the ring now, in one device pass over the two token sets and
+// without any key: {count, movedHashes, lo, hi, before, after} (Uint32Arrays; rows of max(n,1)
+// owner ids, 0xFFFFFFFF = none; movedHashes: how many of the 2^32 hash values moved).
+// movedRangeNames() turns that into [{lo, hi, before: [names], after: [names]}].
+HashRing.prototype.movedRanges = function movedRanges(snap, n) {
+    n = n === undefined ? 1 : n | 0;
+    return native.ringMovedRanges(this._h, snap._h, n);
+};
+
+HashRing.prototype.movedRangeNames = function movedRangeNames(ranges, n) {
+    var w = n > 1 ? n : 1, out = new Array(ranges.lo.length), self = this;
+    function row(a, j) {
+        var r = [];
+        for (var q = 0; q < w && a[j * w + q] !== 0xFFFFFFFF; q++) { r.push(self.ownerName(a[j * w + q])); }
+        return r;
+    }
+    for (var j = 0; j < out.length; j++) {
+        out[j] = {lo: ranges.lo[j], hi: ranges.hi[j], before: row(ranges.before, j), after: row(ranges.after, j)};
+    }
+    return out;
+};
+
+// The snapshot's sorted tokens and their owner ids: {tokens: Uint32Array, owners: Uint32Array}.
+RingSnapshot.prototype.dump = function dump() { return native.ringSnapDump(this._h); };
+
 // How even is the ring? ownerLoad(keys, n): {server name: [key count per lookupN(key, n) slot]}
 // (slot 0: as primary) for the servers now in the ring, counted on the device without keeping
 // the owner rows; ownerShare(): {server name: how many of the 2^32 hash values it owns} (the

@@ -727,6 +727,85 @@ static napi_value js_ring_owner_share(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* ringMovedRanges(h, snap, n) -> {count, movedHashes, lo, hi, before, after}: the hash intervals
+ * [lo, hi] (inclusive, ascending) on which the lookupN(h, n) row under the snapshot differs from
+ * the row now (rp_ring_moved_ranges), with the two rows of max(n,1) owner ids each (0xFFFFFFFF =
+ * none). movedHashes is a Number: exact, it is at most 2^32. */
+static napi_value js_ring_moved_ranges(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    handle_t *h = get_handle(env, argv[0], 1);
+    if (!h) return NULL;
+    handle_t *sh = get_handle(env, argv[1], 4);
+    if (!sh) return NULL;
+    rp_ring *r = (rp_ring *)h->p;
+    const rp_ring_snap *snap = (const rp_ring_snap *)sh->p;
+    int32_t nrep = 0;
+    NAPI_OK(napi_get_value_int32(env, argv[2], &nrep));
+    uint32_t tb = 0, ta = 0;
+    RP_OK(rp_ring_snap_info(snap, &tb, NULL, NULL, NULL));
+    RP_OK(rp_ring_token_count(r, &ta));
+    const size_t w = nrep > 1 ? (size_t)nrep : 1u, cap = (size_t)tb + ta + 1; /* holds every run */
+    uint32_t *lo = (uint32_t *)malloc(4 * cap), *hi = (uint32_t *)malloc(4 * cap),
+             *br = (uint32_t *)malloc(4 * cap * w), *ar = (uint32_t *)malloc(4 * cap * w);
+    uint32_t count = 0;
+    uint64_t moved = 0;
+    int rc = (lo && hi && br && ar) ? rp_ring_moved_ranges(r, snap, nrep, (uint32_t)cap, lo, hi, br, ar, &count, &moved)
+                                    : -2;
+    napi_value out = NULL;
+    if (!rc) {
+        void *dl = NULL, *dh = NULL, *db = NULL, *da = NULL;
+        napi_value vl = new_typed(env, napi_uint32_array, count, 4, &dl);
+        napi_value vh = new_typed(env, napi_uint32_array, count, 4, &dh);
+        napi_value vb = new_typed(env, napi_uint32_array, count * w, 4, &db);
+        napi_value va = new_typed(env, napi_uint32_array, count * w, 4, &da);
+        if (count) {
+            memcpy(dl, lo, 4 * (size_t)count);
+            memcpy(dh, hi, 4 * (size_t)count);
+            memcpy(db, br, 4 * (size_t)count * w);
+            memcpy(da, ar, 4 * (size_t)count * w);
+        }
+        napi_value vm;
+        napi_create_double(env, (double)moved, &vm);
+        napi_create_object(env, &out);
+        napi_set_named_property(env, out, "count", make_u32(env, count));
+        napi_set_named_property(env, out, "movedHashes", vm);
+        napi_set_named_property(env, out, "lo", vl);
+        napi_set_named_property(env, out, "hi", vh);
+        napi_set_named_property(env, out, "before", vb);
+        napi_set_named_property(env, out, "after", va);
+    }
+    free(lo);
+    free(hi);
+    free(br);
+    free(ar);
+    if (rc == -2) {
+        napi_throw_error(env, NULL, "allocation failed");
+        return NULL;
+    }
+    RP_OK(rc);
+    return out;
+}
+
+/* ringSnapDump(snap) -> {tokens: Uint32Array, owners: Uint32Array}: the snapshot's sorted tokens
+ * and their owner ids (rp_ring_snap_dump). */
+static napi_value js_ring_snap_dump(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    handle_t *h = get_handle(env, argv[0], 4);
+    if (!h) return NULL;
+    const rp_ring_snap *snap = (const rp_ring_snap *)h->p;
+    uint32_t m = 0;
+    RP_OK(rp_ring_snap_info(snap, &m, NULL, NULL, NULL));
+    void *dt = NULL, *dw = NULL;
+    napi_value vt = new_typed(env, napi_uint32_array, m, 4, &dt);
+    napi_value vo = new_typed(env, napi_uint32_array, m, 4, &dw);
+    if (m) RP_OK(rp_ring_snap_dump(snap, (uint32_t *)dt, (uint32_t *)dw, m));
+    napi_value out;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "tokens", vt);
+    napi_set_named_property(env, out, "owners", vo);
+    return out;
+}
+
 /* lookupNBatch(h, keys[], n) -> arrays of names, lookupN() of every key (:157-189). */
 static napi_value js_ring_lookupn(napi_env env, napi_callback_info info) {
     ARGS(3);
@@ -1461,6 +1540,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringMovedKeys", NULL, js_ring_moved_keys, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerLoad", NULL, js_ring_owner_load, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerShare", NULL, js_ring_owner_share, NULL, NULL, NULL, napi_default, NULL},
+        {"ringMovedRanges", NULL, js_ring_moved_ranges, NULL, NULL, NULL, napi_default, NULL},
+        {"ringSnapDump", NULL, js_ring_snap_dump, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later);
     return exports;
