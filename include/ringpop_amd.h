@@ -385,7 +385,8 @@ typedef struct rp_damp_config {
  * config. Call it where the reference constructs Membership (initMembership, index.js:399-418). */
 int rp_members_damp_configure(rp_members *m, const rp_damp_config *cfg);
 /* The last update batch, per change in batch order: the member's dampScore after the change and
- * whether 'suppressLimitExceeded' fired (member.js:141-152). k <= that batch's size. */
+ * whether 'suppressLimitExceeded' fired (member.js:141-152). k <= that batch's size; an empty
+ * batch (k = 0) is a batch too, so after one any k > 0 is RP_EINVAL. */
 int rp_members_damp_last(rp_members *m, double *score, uint8_t *exceeded, uint32_t k);
 /* The decayer tick at Date.now() = now_ms (host form syncs; _dev is stream-ordered). */
 int rp_members_damp_decay(rp_members *m, int64_t now_ms);

@@ -1440,6 +1440,7 @@ struct Members {
         }
         if (s != st) RP_HIP(hipStreamSynchronize(st));
         if (!k) {
+            d_out_k = 0;  // the last batch is now this empty one: damp_last has no scores to hand back
             RP_HIP(hipMemsetAsync(napplied.p, 0, sizeof(uint32_t), s));
             if (n_applied_out) RP_HIP(hipMemsetAsync(n_applied_out, 0, sizeof(uint32_t), s));
             return;

@@ -2,7 +2,8 @@
 scoring (lib/membership/member.js:45-66,133-153, index.js:249-324,374-383) in node here (needs
 /root/reference and the oracle/_ref shims; never runs on the GPU box).
 
-    python tests/golden/make_damp_golden.py
+    python tests/golden/make_damp_golden.py        # damp_golden.json
+    python tests/golden/make_damp_golden.py hot    # damp_hot_golden.json (the hot-address case)
 
 Inputs come from a seeded Python RNG: addresses, batches of (address, status, incarnation)
 changes, clock steps, decayer ticks, the ready/set bootstrap path and per-case config values.
@@ -15,6 +16,7 @@ import json
 import os
 import random
 import subprocess
+import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -128,8 +130,26 @@ def make_cases():
     ]
 
 
-def main():
-    cases = make_cases()
+def hot_case():
+    """The hot-address shape (tests/damp_cases.py golden_hot_inputs): one batch with an address past
+    1,024 changes and addresses with 15, 16, 17 and 60, the local member hot, a member created
+    inside the hot batch; then every hot address once, a decay, and a smaller hot batch."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import damp_cases
+    c = damp_cases.golden_hot_inputs()
+    ops = []
+    for op in c["ops"]:
+        if op["type"] == "decay":
+            ops.append({"type": "decay", "now": op["now"]})
+            continue
+        ops.append({"type": "update", "now": op["now"], "isLocal": False,
+                    "changes": [[c["names"][int(a)], STATUSES[int(s)], int(i)]
+                                for a, s, i in zip(op["ids"], op["status"], op["inc"])]})
+    return {"name": "hot", "local": c["local"], "config": c["config"], "ops": ops}
+
+
+def main(cases=None, out="damp_golden.json"):
+    cases = cases or make_cases()
     env = dict(os.environ, NODE_PATH=os.path.join(REPO, "oracle", "_ref", "node_modules"))
     with tempfile.TemporaryDirectory() as td:
         fin, fout = os.path.join(td, "in.json"), os.path.join(td, "out.json")
@@ -140,10 +160,18 @@ def main():
             res = json.load(f)
     for c, o in zip(cases, res["cases"]):
         c["out"] = o["ops"]
-    with open(os.path.join(HERE, "damp_golden.json"), "w") as f:
+    with open(os.path.join(HERE, out), "w") as f:
         json.dump({"generator": "tests/golden/make_damp_golden.py + ref_damp.js over lib/membership/{index,member}.js",
                    "node": res["node"], "cases": cases}, f)
 
 
+def main_hot():
+    """damp_hot_golden.json, a file of its own: damp_golden.json stays as it is."""
+    main([hot_case()], "damp_hot_golden.json")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["hot"]:
+        main_hot()
+    else:
+        main()

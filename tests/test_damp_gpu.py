@@ -12,15 +12,20 @@ import numpy as np
 import pytest
 
 import golden_util as gu
+from damp_model import DampModel
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 STAT = {"alive": 0, "suspect": 1, "faulty": 2, "leave": 3}
 
 
-def run_case(rpa, case):
-    m = rpa.Membership(whoami=case["local"])
+def run_case(rpa, orc, case, make=None):
+    """make (optional): builds the handle (tests/test_damp_paths_gpu.py runs the cases on every fold
+    path). The per-change scores of damp_last are compared with the sequential model
+    (tests/damp_model.py) fed with the reference's applied lists."""
+    m = make(case["local"]) if make else rpa.Membership(whoami=case["local"])
     m.damp_configure(case["config"])
+    model = DampModel(orc, case["config"], local=case["local"])
     for k, (op, o) in enumerate(zip(case["ops"], case["out"])):
         now = op["now"]
         sup = []
@@ -28,17 +33,24 @@ def run_case(rpa, case):
             m.set_ready(op["value"])
         elif op["type"] == "set":
             m.set()
+            model.set([x[0] for x in o["members"]])
         elif op["type"] == "decay":
             m.damp_decay(now)
+            model.decay(now)
         else:
             ch = op["changes"]
+            mapp = np.zeros(len(ch), np.uint8)
+            mapp[o["applied"]] = 1
+            msc, mexc = model.update([c[0] for c in ch], mapp, now)
             ids = m.intern([c[0] for c in ch])
             app, _, _, _ = m.update_ids(ids, [STAT[c[1]] for c in ch], [c[2] for c in ch], now_ms=now,
                                         is_local=op.get("isLocal", False))
             assert list(np.flatnonzero(app)) == o["applied"], (case["name"], k)
             if len(o["applied"]) or m.is_ready or op.get("isLocal"):
-                _, exc = m.damp_last(len(ch))
+                sc, exc = m.damp_last(len(ch))
                 sup = [ch[i][0] for i in np.flatnonzero(exc)]
+                assert np.array_equal(sc.view(np.uint64), msc.view(np.uint64)), (case["name"], k)
+                assert np.array_equal(exc, mexc), (case["name"], k)
         assert sup == o["suppressed"], (case["name"], k)
         sc, ls, ts = m.damp_dump()
         ex, _, _ = m.dump()
@@ -53,9 +65,9 @@ def run_case(rpa, case):
 
 @pytest.mark.parametrize("name", ["defaults", "flap", "half-life", "min-floor", "disabled", "fractional",
                                   "bootstrap", "wide"])
-def test_damp_matches_reference_golden(gpu, name):
+def test_damp_matches_reference_golden(gpu, orc, name):
     case = next(c for c in gu.load("damp_golden.json")["cases"] if c["name"] == name)
-    run_case(gpu, case)
+    run_case(gpu, orc, case)
 
 
 def test_decay_sweep_vs_oracle_at_scale(gpu, orc):

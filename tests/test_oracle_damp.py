@@ -1,14 +1,17 @@
-"""The damp-scoring oracle (oracle/orc_damp.c) against the reference's own run
-(tests/golden/damp_golden.json: lib/membership/{index,member}.js in node, make_damp_golden.py).
+"""The damp-scoring oracle (oracle/orc_damp.c) and the sequential damp model (tests/damp_model.py)
+against the reference's own run (tests/golden/damp_golden.json and damp_hot_golden.json:
+lib/membership/{index,member}.js in node, make_damp_golden.py).
 CPU only. Bit-exact: every Math.pow(Math.E, y) the engine evaluated, and every member's
 dampScore / lastUpdateDampScore / lastUpdateTimestamp after every op, plus the order of
 'suppressLimitExceeded' events."""
 import math
 import struct
 
+import numpy as np
 import pytest
 
 import golden_util as gu
+from damp_model import DampModel
 
 STATUSES = ["alive", "suspect", "faulty", "leave"]
 
@@ -19,7 +22,8 @@ def bits(x):
 
 @pytest.fixture(scope="module")
 def golden():
-    return gu.load("damp_golden.json")
+    # damp_hot_golden.json: the hot-address case (one address past 1,024 changes in a batch)
+    return {"cases": gu.load("damp_golden.json")["cases"] + gu.load("damp_hot_golden.json")["cases"]}
 
 
 def test_pow_matches_engine_bit_for_bit(orc, golden):
@@ -39,32 +43,25 @@ def test_js_round_half_up(orc):
 
 
 def replay(orc, case):
-    """The reference's damp bookkeeping from the applied lists, with the oracle's arithmetic."""
-    cfg = orc.damp_cfg(case["config"])
-    state, snaps, events = {}, [], []
+    """The reference's damp bookkeeping from the applied lists (tests/damp_model.py, the model the
+    GPU tests compare the device with), with the oracle's arithmetic."""
+    model = DampModel(orc, case["config"], local=case["local"])
+    snaps, events = [], []
     for op, o in zip(case["ops"], case["out"]):
         now = op["now"]
         ev = []
         if op["type"] == "update":
-            for i in o["applied"]:
-                a = op["changes"][i][0]
-                if a not in state:
-                    state[a] = [cfg.initial, cfg.initial, 0]
-                    continue
-                st = state[a]
-                if cfg.enabled and a != case["local"]:
-                    s, exc = orc.damp_penalized(cfg, st[1], st[2], now)
-                    st[0] = st[1] = s
-                    if exc:
-                        ev.append(a)
-                st[2] = now
+            addrs = [c[0] for c in op["changes"]]
+            app = np.zeros(len(addrs), np.uint8)
+            app[o["applied"]] = 1
+            _, flag = model.update(addrs, app, now)
+            ev = [addrs[i] for i in np.flatnonzero(flag)]
         elif op["type"] == "set":
-            assert not state
-            state = {m[0]: [cfg.initial, cfg.initial, 0] for m in o["members"]}
+            assert not model.state
+            model.set([m[0] for m in o["members"]])
         elif op["type"] == "decay":
-            for st in state.values():
-                st[0] = orc.damp_decayed(cfg, st[1], st[2], now)
-        snaps.append({a: tuple(v) for a, v in state.items()})
+            model.decay(now)
+        snaps.append(model.snapshot())
         events.append(ev)
     return snaps, events
 
