@@ -273,6 +273,58 @@ int rp_ring_snap_moved_ranges(const rp_ring_snap *before, rp_ring_snap *after, i
 /* The snapshot's sorted (token, owner) arrays, as rp_ring_dump gives them for a ring. */
 int rp_ring_snap_dump(const rp_ring_snap *s, uint32_t *tokens, uint32_t *owners, uint32_t cap);
 
+/* Hand-off plan: which keys to send to whom after a ring change (what an application does on
+ * ringChanged). For key i let B be its lookupN(key, nrep) row under `before` and A its row under
+ * r: exactly the rows rp_ring_moved_keys* compares (W = max(nrep, 1) slots padded with
+ * RP_NULL_ID, each side with its own min(nrep, server count), nrep <= 0 keeps lookupn's
+ * single-step form). Every server in a key's row holds the key.
+ *   src(i)     the first entry of B, in slot order, whose server is in r's server set at call
+ *              time (not: in A); RP_NULL_ID if none (an orphan: the key comes from elsewhere)
+ *   gained     the non-null A[q] that occur nowhere in B, in slot order
+ *   transfers  one record (key = i, dst = A[q], src = src(i), slot = q) per gained entry. A key
+ *              whose rows differ but whose A gains nothing (its row only shrank, or only changed
+ *              order) is moved for rp_ring_moved_keys and has no record here.
+ *   only_src   not RP_NULL_ID: only keys with src(i) == only_src produce records (what this
+ *              server has to push). RP_NULL_ID keeps every record, orphans included.
+ * The record stream is every record in (key index, slot) order; *count is its full length and
+ * the result describes its first T = min(count, cap) records (cap may cut between two records of
+ * one key), grouped by destination:
+ *   dests[0 .. *ndest)        the distinct dst among those T records, ascending by server id
+ *   group_off[0 .. *ndest]    group g is entries [group_off[g], group_off[g+1]) of key_idx / src /
+ *                             slot; group_off[*ndest] == T
+ *   key_idx / src / slot      per record; inside a group key indices are strictly ascending (a
+ *                             key gains a server at most once). src and slot may be NULL.
+ * Capacities: dests min(cap, rp_ring_id_bound) entries, group_off one more, key_idx / src / slot
+ * cap each; nothing at or past them is touched. Results, not errors: n == 0, an empty ring now
+ * (nothing is gained) and cap == 0 (counts only; the arrays may then be NULL) give *ndest = 0 and
+ * group_off[0] = 0 (where group_off is given); an empty `before` gives every key its whole A with
+ * src = RP_NULL_ID. nrep > 8, n * W >= 2^32 (the look-back word carries 32 bits of running
+ * count), a null handle, a snapshot on another device, and an only_src that is neither
+ * RP_NULL_ID nor below rp_ring_id_bound return RP_EINVAL with nothing written.
+ * One pass reads and hashes each key once, searches both rings and writes the record stream to a
+ * scratch the ring owns (13 bytes per record slot, allocated when it first grows, never per call
+ * after that); a stable radix sort by dst then groups it. The _dev form takes device buffers
+ * (d_ndest, d_count one uint32 each), is stream-ordered and never syncs with the host, except
+ * that a stream other than the ring's own first waits for the ring's pending rebuilds (as
+ * rp_ring_moved_keys_dev does). It cannot know the record count on the host, so its grouping
+ * passes run over min(cap, n * W) slots: their cost follows cap. Size cap from a count-only call
+ * (cap = 0) or from the moved share (rp_ring_moved_ranges) rather than from n * W. The host forms
+ * read the count back after the first pass and group exactly T records. */
+int rp_ring_handoff_dev(rp_ring *r, const rp_ring_snap *before,
+                        const uint8_t *d_keys, const uint64_t *d_off, uint32_t stride, uint64_t n,
+                        int32_t nrep, uint32_t only_src, uint32_t cap,
+                        uint32_t *d_dests, uint32_t *d_group_off, uint32_t *d_key_idx, uint32_t *d_src,
+                        uint8_t *d_slot, uint32_t *d_ndest, uint32_t *d_count, void *stream);
+int rp_ring_handoff(rp_ring *r, const rp_ring_snap *before, const char *keys, const uint64_t *off,
+                    uint32_t stride, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap,
+                    uint32_t *dests, uint32_t *group_off, uint32_t *key_idx, uint32_t *src,
+                    uint8_t *slot, uint32_t *ndest, uint32_t *count);
+/* Same with a caller hashFunc's key hashes (options.hashFunc, lib/ring/index.js:29). */
+int rp_ring_handoff_hashes(rp_ring *r, const rp_ring_snap *before, const uint32_t *hashes, uint64_t n,
+                           int32_t nrep, uint32_t only_src, uint32_t cap,
+                           uint32_t *dests, uint32_t *group_off, uint32_t *key_idx, uint32_t *src,
+                           uint8_t *slot, uint32_t *ndest, uint32_t *count);
+
 /* ------------------------------------------------------------------ Membership
  * Replaces the hot path of lib/membership/index.js Membership: update (249-324) with the
  * Member.evaluateUpdate rules (lib/membership/member.js:71-202) and computeChecksum /

@@ -90,6 +90,9 @@ SIGNATURES = {
     "rp_ring_snap_moved_ranges_dev": (_INT, [_P, _P, _I32, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "rp_ring_snap_moved_ranges": (_INT, [_P, _P, _I32, _U32, _P, _P, _P, _P, _P, _P]),
     "rp_ring_snap_dump": (_INT, [_P, _P, _P, _U32]),
+    "rp_ring_handoff_dev": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_handoff": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_handoff_hashes": (_INT, [_P, _P, _P, _U64, _I32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "rp_members_create": (_INT, [_U32, _INT, _P]),
     "rp_members_destroy": (_INT, [_P]),
     "rp_members_intern": (_INT, [_P, _P, _P, _U32, _P]),
@@ -546,6 +549,61 @@ class HashRing:
                   off_ptr=None, stream=None):
         check(lib().rp_ring_moved_keys_dev(self._h, before._h, keys_ptr, off_ptr, stride, n, nrep, cap, idx_ptr,
                                            before_ptr, after_ptr, count_ptr, stream))
+
+    # -- hand-off plan (what to send to whom after ringChanged)
+    def handoff_ids(self, keys, before, n=1, only_src=None, cap=None):
+        """(dests, group_off, key_idx, src, slot): the transfers that bring every key's lookupN(key, n)
+        row of now up to date from its row under the snapshot `before`, grouped by destination id
+        (ascending); group g is entries group_off[g]:group_off[g+1] of key_idx / src / slot. src is
+        the first holder before that is still in the ring (NULL_ID: none, an orphan). only_src keeps
+        the transfers that server has to send. cap bounds the records returned (the first cap of the
+        (key, slot) ordered stream); `handoff_count` holds the full count."""
+        w = max(int(n), 1)
+        cnt, nd = ctypes.c_uint32(), ctypes.c_uint32()
+        if self.hashFunc is not None:
+            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
+            k = len(hs)
+        else:
+            blob, off, stride, k = self._key_pack(keys)
+        c = k * w if cap is None else min(int(cap), k * w)
+        osrc = NULL_ID if only_src is None else int(only_src)
+        bound = min(c, self.id_bound())
+        dests = np.empty(max(bound, 1), dtype=np.uint32)
+        goff = np.zeros(bound + 1, dtype=np.uint32)
+        kidx = np.empty(max(c, 1), dtype=np.uint32)
+        src = np.empty(max(c, 1), dtype=np.uint32)
+        slot = np.empty(max(c, 1), dtype=np.uint8)
+        outs = (dests.ctypes.data, goff.ctypes.data, kidx.ctypes.data, src.ctypes.data, slot.ctypes.data,
+                ctypes.byref(nd), ctypes.byref(cnt))
+        if self.hashFunc is not None:
+            check(lib().rp_ring_handoff_hashes(self._h, before._h, hs.ctypes.data, k, int(n), osrc, c, *outs))
+        else:
+            check(lib().rp_ring_handoff(self._h, before._h, blob.ctypes.data, _ptr(off), stride, k, int(n), osrc, c,
+                                        *outs))
+        self.handoff_count = cnt.value
+        t, g = min(cnt.value, c), nd.value
+        return dests[:g], goff[:g + 1], kidx[:t], src[:t], slot[:t]
+
+    def handoffPlan(self, keys, before, n=1, whoami=None):
+        """{destination name: [(key, source name or None), ...]} after a ring change since the
+        snapshot `before`: destinations ascending by id, each list in input order. whoami: only what
+        that server has to send (it is the first surviving holder of those keys)."""
+        keys = [k if isinstance(k, (bytes, np.ndarray)) else str(k) for k in keys]
+        only = None
+        if whoami is not None:
+            only = self.server_id(whoami)
+            if only == NULL_ID:
+                return {}
+        dests, goff, kidx, src, _ = self.handoff_ids(keys, before, n, only_src=only)
+        return {self.name(d): [(keys[i], None if s == NULL_ID else self.name(s))
+                               for i, s in zip(kidx[goff[g]:goff[g + 1]], src[goff[g]:goff[g + 1]])]
+                for g, d in enumerate(dests)}
+
+    def handoff_dev(self, before, keys_ptr, n, nrep, cap, dests_ptr, goff_ptr, key_idx_ptr, src_ptr, slot_ptr,
+                    ndest_ptr, count_ptr, only_src=NULL_ID, stride=36, off_ptr=None, stream=None):
+        check(lib().rp_ring_handoff_dev(self._h, before._h, keys_ptr, off_ptr, stride, n, nrep, only_src, cap,
+                                        dests_ptr, goff_ptr, key_idx_ptr, src_ptr, slot_ptr, ndest_ptr, count_ptr,
+                                        stream))
 
     # -- owner load and hash-space share (how even is the ring?)
     def id_bound(self):

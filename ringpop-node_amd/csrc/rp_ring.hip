@@ -2452,6 +2452,16 @@ struct RangeScratch {
     void use_on(hipStream_t st) { order.use_on(st); }
 };
 
+// The scratch of the hand-off calls of one ring, ordered across streams in the same way.
+struct HandoffScratch {
+    DevBuf<uint32_t> key, dst, src, perm;  // the record stream's columns, and the sort's values
+    DevBuf<uint8_t> slot;
+    DevBuf<uint32_t> rank;  // per server id: 1 if a destination, then the exclusive scan (its group)
+    DevBuf<uint32_t> io;    // the host forms' outputs
+    StreamOrder order;
+    void use_on(hipStream_t st) { order.use_on(st); }
+};
+
 struct Ring {
     int device = 0;
     hipStream_t st = nullptr;
@@ -2519,6 +2529,8 @@ struct Ring {
     Scratch ws;
     LoadScratch load_ws;  // owner load / share
     RangeScratch range_ws;  // moved ranges
+    HandoffScratch handoff_ws;  // hand-off plan
+    uint32_t inring_n = 0;  // the ids d_inring covers (ring_compute_checksum copies in_ring at every change)
 
     RingView view() const {
         return RingView{tok.p, own.p, bstart.p, M, 32u - bbits};
@@ -2736,6 +2748,7 @@ static void ring_compute_checksum(Ring& r) {
     const uint32_t n = r.nt.size();
     r.d_inring.reserve((uint64_t)n + 1);
     if (n) RP_HIP(hipMemcpyAsync(r.d_inring.p, r.in_ring.data(), n, hipMemcpyHostToDevice, r.st));
+    r.inring_n = n;
     r.flag.reserve((uint64_t)n + 1);
     r.pos.reserve((uint64_t)n + 1);
     r.ck_buf.reserve(r.nt.h_bytes.size() + n + 16);
@@ -3500,6 +3513,300 @@ static void moved_keys(Ring& r, const Snap& s, const uint8_t* keys, const uint64
         else RP_MOVED(8, 1, false);
     }
 #undef RP_MOVED
+}
+
+// ------------------------------------------------------------- hand-off plan
+// What to send to whom after a ring change (rp_ring_handoff*). k_handoff is k_moved's pass with
+// another tail: per key the two rows (moved_find / moved_walk, the same tile = ticket scheme and
+// key staging), then in registers the gained mask (each entry of the row now against the whole
+// row before) and, for keys that gain a server only, the source: the first holder before that is
+// in the ring now (one byte of d_inring per holder until one is live). A key emits one record per
+// gained server, so the compaction is multi-record: a key's first record has rank
+// sum_j popcount(ballot(c > j) & lanes below) among its wave's keys of a slot, c its record
+// count; (slot, wave) prefixes in LDS; the tile's offset by decoupled look-back. The record
+// stream (key index, dst, src, slot) goes to the ring's scratch in (key, slot) order below cap;
+// a stable sort by dst then groups it.
+template <int MAXN, int KPL, bool FIXED>
+__global__ __launch_bounds__(kLkThreads) void k_handoff(const uint8_t* __restrict__ keys,
+                                                        const uint64_t* __restrict__ off, uint32_t stride,
+                                                        const uint32_t* __restrict__ hashes, uint32_t n, RingView bv,
+                                                        int npb, RingView av, int npa,
+                                                        const uint8_t* __restrict__ inring, uint32_t ninring,
+                                                        uint32_t only_src, uint32_t cap, uint32_t* __restrict__ rkey,
+                                                        uint32_t* __restrict__ rdst, uint32_t* __restrict__ rsrc,
+                                                        uint8_t* __restrict__ rslot, uint32_t* __restrict__ count,
+                                                        uint64_t* __restrict__ lb, unsigned long long* ctr,
+                                                        uint64_t tag, uint32_t ntiles, uint32_t* err) {
+    constexpr int TILE = kLkThreads * KPL;
+    constexpr int W4 = 9;                    // dwords per 36-byte key
+    constexpr int V4 = TILE * W4 / 4;        // 16-B vectors per full tile
+    constexpr int PER = (V4 + kLkThreads - 1) / kLkThreads;
+    static_assert((TILE * W4) % 4 == 0, "tile must be a whole number of 16-B vectors");
+    __shared__ __attribute__((aligned(16))) uint32_t sk[FIXED ? TILE * W4 : 4];
+    __shared__ uint32_t s_cnt[KPL * (kLkThreads / 64)];
+    __shared__ uint32_t s_excl;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t tile = take_unit(ctr, ntiles, err);  // (syncs)
+    if (tile >= ntiles) return;  // a ticket count out of step (reported): never write out of bounds
+    const uint32_t base = tile * (uint32_t)TILE;
+    const uint32_t cnt = n - base < (uint32_t)TILE ? n - base : (uint32_t)TILE;
+    if constexpr (FIXED) {  // (k_moved's staging)
+        const uint8_t* src = keys + (uint64_t)base * 36u;
+        if (cnt == (uint32_t)TILE && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
+            const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+            u32x4* d4 = reinterpret_cast<u32x4*>(sk);
+            u32x4 pre[PER];
+#pragma unroll
+            for (int q = 0; q < PER; q++) {
+                const int k = tid + q * kLkThreads;
+                if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
+            }
+#pragma unroll
+            for (int q = 0; q < PER; q++) {
+                const int k = tid + q * kLkThreads;
+                if (k < V4) d4[k] = pre[q];
+            }
+        } else {
+            const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
+            for (uint32_t k = tid; k < cnt * W4; k += kLkThreads) sk[k] = s1[k];
+        }
+        __syncthreads();
+    }
+    uint32_t ra[KPL][MAXN], gm[KPL], sr[KPL];  // the row now, its gained slots (bit q), the source
+#pragma unroll
+    for (int q = 0; q < KPL; q++) {
+        const uint32_t kl = (uint32_t)(q * kLkThreads + tid);
+        gm[q] = 0;
+        sr[q] = NIL;
+#pragma unroll
+        for (int j = 0; j < MAXN; j++) ra[q][j] = NIL;
+        if (kl < cnt) {
+            uint32_t h;
+            if constexpr (FIXED) {
+                uint32_t w[W4];
+#pragma unroll
+                for (int j = 0; j < W4; j++) w[j] = sk[kl * W4 + j];
+                h = fh::hash32_words<36>(w);
+            } else if (hashes) {
+                h = hashes[base + kl];
+            } else {
+                const uint64_t k = (uint64_t)base + kl;
+                uint64_t b, e;
+                if (stride) {
+                    b = k * stride;
+                    e = b + stride;
+                } else {
+                    b = off[k];
+                    e = off[k + 1];
+                }
+                h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
+            }
+            uint32_t rb[MAXN];
+            moved_walk<MAXN>(bv, moved_find(bv, h), npb, rb);
+            moved_walk<MAXN>(av, moved_find(av, h), npa, ra[q]);
+            uint32_t g = 0;
+#pragma unroll
+            for (int a = 0; a < MAXN; a++) {
+                bool held = false;
+#pragma unroll
+                for (int b = 0; b < MAXN; b++) held |= ra[q][a] == rb[b];
+                if (ra[q][a] != NIL && !held) g |= 1u << a;
+            }
+            if (g) {
+                uint32_t s = NIL;
+#pragma unroll
+                for (int b = 0; b < MAXN; b++)
+                    if (s == NIL && rb[b] < ninring && inring[rb[b]]) s = rb[b];  // (NIL >= ninring)
+                sr[q] = s;
+                if (only_src != NIL && s != only_src) g = 0;
+            }
+            gm[q] = g;
+        }
+    }
+    // a key's first record among the records of its wave's 64 keys of slot q, and the
+    // (slot, wave) segment totals
+    const uint64_t lt_mask = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    uint32_t rank[KPL];
+#pragma unroll
+    for (int q = 0; q < KPL; q++) {
+        const int c = __popc(gm[q]);
+        uint32_t rk = 0, tot = 0;
+#pragma unroll
+        for (int j = 0; j < MAXN; j++) {
+            const uint64_t m = __ballot(c > j);
+            rk += (uint32_t)__popcll(m & lt_mask);
+            tot += (uint32_t)__popcll(m);
+        }
+        rank[q] = rk;
+        if (lane == 0) s_cnt[q * (kLkThreads / 64) + wave] = tot;
+    }
+    __syncthreads();
+    uint32_t pre[KPL], total = 0;
+#pragma unroll
+    for (int s = 0; s < KPL * (kLkThreads / 64); s++) {
+        if ((s & (kLkThreads / 64 - 1)) == wave) pre[s / (kLkThreads / 64)] = total;
+        total += s_cnt[s];
+    }
+    if (tid == 0) lb_store(lb + tile, tag | (tile == 0 ? kLbP : kLbA) | total);
+    if (tid < 64) {
+        const uint32_t excl = lookback_wave(lb, tile, tag, err);
+        if (tid == 0) {
+            if (tile > 0) lb_store(lb + tile, tag | kLbP | (excl + total));
+            s_excl = excl;
+            if (tile == ntiles - 1) *count = excl + total;
+        }
+    }
+    __syncthreads();
+    const uint32_t gbase = s_excl;
+#pragma unroll
+    for (int q = 0; q < KPL; q++) {
+        uint32_t p = gbase + pre[q] + rank[q];
+#pragma unroll
+        for (int j = 0; j < MAXN; j++) {
+            if ((gm[q] >> j) & 1u) {
+                if (p < cap) {  // (also bounds every write if a look-back wait gave up)
+                    rkey[p] = base + (uint32_t)(q * kLkThreads + tid);
+                    rdst[p] = ra[q][j];
+                    rsrc[p] = sr[q];
+                    rslot[p] = (uint8_t)j;
+                }
+                p++;
+            }
+        }
+    }
+}
+
+template <int MAXN, int KPL, bool FIXED, class... A>
+static void launch_handoff_k(uint32_t n, hipStream_t st, Scratch& ws, A... args) {
+    const uint32_t ntiles = (uint32_t)(((uint64_t)n + kLkThreads * KPL - 1) / (kLkThreads * KPL));
+    const LookBack L = lookback_prepare(ws, ntiles, st);
+    hipLaunchKernelGGL((k_handoff<MAXN, KPL, FIXED>), dim3(ntiles), dim3(kLkThreads), 0, st, args..., L.words,
+                       L.ticket, L.tag, ntiles, L.err);
+    RP_HIP(hipGetLastError());
+}
+
+// Grouping: the records sorted by dst (stable, so (key, slot) order inside a group). T =
+// min(*count, cap) is read on the device; threads past T exit.
+// present[d] = 1 for every dst among the first T sorted records (the run heads)
+__global__ void k_handoff_heads(const uint32_t* __restrict__ sd, const uint32_t* __restrict__ count, uint32_t cap,
+                                uint32_t id_bound, uint32_t* __restrict__ present) {
+    const uint32_t T = *count < cap ? *count : cap;
+    const uint32_t gstride = gridDim.x * blockDim.x;
+    for (uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; p < T; p += gstride) {
+        const uint32_t d = sd[p];
+        if ((p == 0 || sd[p - 1] != d) && d < id_bound) present[d] = 1u;
+    }
+}
+
+// rank = the exclusive scan of present (rank[id_bound] = the number of destinations): dests and
+// group_off from the run heads, and the record columns gathered through the sort's permutation
+__global__ void k_handoff_emit(const uint32_t* __restrict__ sd, const uint32_t* __restrict__ perm,
+                               const uint32_t* __restrict__ rkey, const uint32_t* __restrict__ rsrc,
+                               const uint8_t* __restrict__ rslot, const uint32_t* __restrict__ count, uint32_t cap,
+                               uint32_t id_bound, const uint32_t* __restrict__ rank, uint32_t* __restrict__ dests,
+                               uint32_t* __restrict__ goff, uint32_t* __restrict__ key_idx,
+                               uint32_t* __restrict__ src, uint8_t* __restrict__ slot, uint32_t* __restrict__ ndest) {
+    const uint32_t T = *count < cap ? *count : cap;
+    const uint32_t gstride = gridDim.x * blockDim.x;
+    const uint32_t t0 = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t0 == 0) {
+        *ndest = T ? rank[id_bound] : 0u;
+        if (T == 0 && goff) goff[0] = 0u;
+    }
+    for (uint32_t p = t0; p < T; p += gstride) {
+        const uint32_t d = sd[p], i = perm[p];
+        key_idx[p] = rkey[i];
+        if (src) src[p] = rsrc[i];
+        if (slot) slot[p] = rslot[i];
+        if (d >= id_bound) continue;  // (no row holds such an id)
+        const uint32_t g = rank[d];
+        if (p == 0 || sd[p - 1] != d) {
+            dests[g] = d;
+            goff[g] = p;
+        }
+        if (p + 1 == T) goff[g + 1] = T;
+    }
+}
+
+// The plan between the snapshot s and the ring now; device outputs as rp_ring_handoff_dev
+// documents. known_count: the host forms read the record count back after the first pass and
+// group exactly min(count, cap) records; the device form groups over min(cap, n * W) slots,
+// padded with a key that sorts last.
+static void handoff(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t* off, uint32_t stride,
+                    const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap,
+                    uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src, uint8_t* slot,
+                    uint32_t* ndest, uint32_t* count, hipStream_t st, bool known_count) {
+    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const uint32_t id_bound = r.nt.size();
+    RP_REQUIRE(nrep <= 8, "handoff: nrep is at most 8 (the rows are compared in registers)");
+    RP_REQUIRE(n < (1ull << 32) && n * W < (1ull << 32), "handoff: n * max(nrep, 1) is at most 2^32-1 records");
+    RP_REQUIRE(s.device == r.device, "handoff: the snapshot lives on another device");
+    RP_REQUIRE(only_src == NIL || only_src < id_bound, "handoff: only_src is not a server id of this ring");
+    RP_REQUIRE(ndest && count, "handoff: null count");
+    RP_REQUIRE(cap == 0 || (dests && goff && key_idx), "handoff: null output buffer");
+    // the ring is rebuilt on r.st; make the caller's stream wait for it
+    if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
+    if (n == 0 || r.M == 0) {  // no key, or nothing to gain
+        RP_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
+        RP_HIP(hipMemsetAsync(ndest, 0, sizeof(uint32_t), st));
+        if (goff) RP_HIP(hipMemsetAsync(goff, 0, sizeof(uint32_t), st));
+        return;
+    }
+    HandoffScratch& ws = r.handoff_ws;
+    ws.use_on(st);
+    const uint32_t m = (uint32_t)std::min<uint64_t>(cap, n * W);  // record slots
+    ws.key.reserve(m);
+    ws.dst.reserve(m);
+    ws.src.reserve(m);
+    ws.slot.reserve(m);
+    ws.perm.reserve(m);
+    ws.rank.reserve((uint64_t)id_bound + 1);
+    const int sort_bits = bits_for(id_bound);
+    // the slots past the record count sort last (0xFF..: above every id in the sorted bits)
+    if (m && !known_count) RP_HIP(hipMemsetAsync(ws.dst.p, 0xFF, 4ull * m, st));
+    const int npb = (int)std::min<int64_t>(nrep, s.server_count), npa = (int)std::min<int64_t>(nrep, r.server_count);
+    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
+    const RingView bv = s.view(), av = r.view();
+#define RP_HANDOFF(MAXN, KPL, FIXED)                                                                                   \
+    launch_handoff_k<MAXN, KPL, FIXED>((uint32_t)n, st, r.ws, keys, off, stride, hashes, (uint32_t)n, bv, npb, av, npa, \
+                                       (const uint8_t*)r.d_inring.p, r.inring_n, only_src, m, ws.key.p, ws.dst.p,       \
+                                       ws.src.p, ws.slot.p, count)
+    if (fixed36) {
+        if (W == 1) RP_HANDOFF(1, 4, true);
+        else if (W <= 4) RP_HANDOFF(4, 4, true);
+        else RP_HANDOFF(8, 2, true);
+    } else {
+        if (W == 1) RP_HANDOFF(1, 1, false);
+        else if (W <= 4) RP_HANDOFF(4, 1, false);
+        else RP_HANDOFF(8, 1, false);
+    }
+#undef RP_HANDOFF
+    if (m == 0) {  // counts only
+        RP_HIP(hipMemsetAsync(ndest, 0, sizeof(uint32_t), st));
+        if (goff) RP_HIP(hipMemsetAsync(goff, 0, sizeof(uint32_t), st));
+        return;
+    }
+    uint32_t g = m;  // the slots to group
+    if (known_count) {
+        uint32_t total = 0;
+        RP_HIP(hipMemcpyAsync(&total, count, 4, hipMemcpyDeviceToHost, st));
+        RP_HIP(hipStreamSynchronize(st));
+        scratch_check(r.ws, st);  // a look-back wait that gave up is an error, not a wrong plan
+        g = std::min(total, m);
+    }
+    if (g) {
+        iota_u32(ws.perm.p, g, st);
+        radix_sort_pairs(ws.dst.p, ws.perm.p, g, 0, sort_bits, st, r.ws);
+    }
+    RP_HIP(hipMemsetAsync(ws.rank.p, 0, 4ull * ((uint64_t)id_bound + 1), st));
+    hipLaunchKernelGGL(k_handoff_heads, dim3(grid_for(g, 256, 256 * 16)), dim3(256), 0, st, ws.dst.p, count, g,
+                       id_bound, ws.rank.p);
+    RP_HIP(hipGetLastError());
+    scan_exclusive_u32(ws.rank.p, ws.rank.p, id_bound, st, r.ws);
+    hipLaunchKernelGGL(k_handoff_emit, dim3(grid_for(g, 256, 256 * 16)), dim3(256), 0, st, ws.dst.p, ws.perm.p,
+                       ws.key.p, ws.src.p, ws.slot.p, count, g, id_bound, ws.rank.p, dests, goff, key_idx, src, slot,
+                       ndest);
+    RP_HIP(hipGetLastError());
 }
 
 // ------------------------------------------------------------- owner load and hash-space share
@@ -4714,6 +5021,107 @@ int rp_ring_moved_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_t*
         const rp::Snap& s = S(before);
         RP_REQUIRE(n == 0 || hashes, "moved_hashes: null hash buffer");
         host_moved(r, s, nullptr, nullptr, 0, hashes, n, nrep, cap, idx, before_rows, after_rows, count);
+    });
+}
+
+// ---- hand-off plan
+
+int rp_ring_handoff_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t* d_keys, const uint64_t* d_off,
+                        uint32_t stride, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap, uint32_t* d_dests,
+                        uint32_t* d_group_off, uint32_t* d_key_idx, uint32_t* d_src, uint8_t* d_slot,
+                        uint32_t* d_ndest, uint32_t* d_count, void* stream) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "handoff_dev: null key buffer");
+        svc_stop(r);
+        rp::handoff(r, s, d_keys, d_off, stride, nullptr, n, nrep, only_src, cap, d_dests, d_group_off, d_key_idx,
+                    d_src, d_slot, d_ndest, d_count, rp::as_stream(stream), false);
+    });
+}
+
+// host-buffer forms: keys (or a caller hashFunc's key hashes) in, the grouped plan out
+static void host_handoff(rp::Ring& r, const rp::Snap& s, const char* keys, const uint64_t* off, uint32_t stride,
+                         const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap,
+                         uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src, uint8_t* slot,
+                         uint32_t* ndest, uint32_t* count) {
+    const uint64_t W = nrep > 1 ? (uint64_t)nrep : 1u;
+    RP_REQUIRE(ndest && count, "handoff: null count");
+    RP_REQUIRE(nrep <= 8, "handoff: nrep is at most 8 (the rows are compared in registers)");
+    RP_REQUIRE(n < (1ull << 32) && n * W < (1ull << 32), "handoff: n * max(nrep, 1) is at most 2^32-1 records");
+    RP_REQUIRE(s.device == r.device, "handoff: the snapshot lives on another device");
+    RP_REQUIRE(only_src == rp::NIL || only_src < r.nt.size(), "handoff: only_src is not a server id of this ring");
+    RP_REQUIRE(cap == 0 || n == 0 || (dests && goff && key_idx), "handoff: null output buffer");
+    svc_stop(r);
+    const uint8_t* dk = nullptr;
+    const uint64_t* doff = nullptr;
+    const uint32_t* dh = nullptr;
+    if (n && hashes) {
+        r.io_a.reserve(n);
+        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
+        dh = r.io_a.p;
+    } else if (n) {
+        const uint64_t bytes = stride ? n * stride : off[n];
+        r.io_keys.reserve(bytes + 16);
+        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
+        dk = r.io_keys.p;
+        if (!stride) {
+            r.io_off.reserve(n + 1);
+            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
+            doff = r.io_off.p;
+        }
+    }
+    // io = [count 1 | ndest 1 | group_off nd+1 | dests nd | key_idx c | src c | slot c bytes],
+    // c = min(cap, n * W), nd = min(c, id bound)
+    const uint64_t c = std::min<uint64_t>(cap, n * W), nd = std::min<uint64_t>(c, r.nt.size());
+    rp::HandoffScratch& ws = r.handoff_ws;
+    ws.use_on(r.st);
+    ws.io.reserve(3 + 2 * nd + 2 * c + (c + 3) / 4);
+    uint32_t* dgo = ws.io.p + 2;
+    uint32_t* dde = dgo + nd + 1;
+    uint32_t* dki = dde + nd;
+    uint32_t* dsr = dki + c;
+    uint8_t* dsl = reinterpret_cast<uint8_t*>(dsr + c);
+    rp::handoff(r, s, dk, doff, stride, dh, n, nrep, only_src, (uint32_t)c, dde, dgo, dki, dsr, dsl, ws.io.p + 1,
+                ws.io.p, r.st, true);
+    uint32_t head[2] = {0, 0};
+    RP_HIP(hipMemcpyAsync(head, ws.io.p, sizeof head, hipMemcpyDeviceToHost, r.st));
+    RP_HIP(hipStreamSynchronize(r.st));
+    rp::scratch_check(r.ws, r.st);
+    *count = head[0];
+    *ndest = head[1];
+    const uint64_t T = std::min<uint64_t>(head[0], c), g = head[1];
+    if (goff) RP_HIP(hipMemcpyAsync(goff, dgo, (g + 1) * 4, hipMemcpyDeviceToHost, r.st));
+    if (T) {
+        RP_HIP(hipMemcpyAsync(dests, dde, g * 4, hipMemcpyDeviceToHost, r.st));
+        RP_HIP(hipMemcpyAsync(key_idx, dki, T * 4, hipMemcpyDeviceToHost, r.st));
+        if (src) RP_HIP(hipMemcpyAsync(src, dsr, T * 4, hipMemcpyDeviceToHost, r.st));
+        if (slot) RP_HIP(hipMemcpyAsync(slot, dsl, T, hipMemcpyDeviceToHost, r.st));
+    }
+    RP_HIP(hipStreamSynchronize(r.st));
+}
+
+int rp_ring_handoff(rp_ring* h, const rp_ring_snap* before, const char* keys, const uint64_t* off, uint32_t stride,
+                    uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap, uint32_t* dests, uint32_t* group_off,
+                    uint32_t* key_idx, uint32_t* src, uint8_t* slot, uint32_t* ndest, uint32_t* count) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(n == 0 || (keys && (stride || off)), "handoff: null key buffer");
+        host_handoff(r, s, keys, off, stride, nullptr, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot,
+                     ndest, count);
+    });
+}
+
+int rp_ring_handoff_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_t* hashes, uint64_t n, int32_t nrep,
+                           uint32_t only_src, uint32_t cap, uint32_t* dests, uint32_t* group_off, uint32_t* key_idx,
+                           uint32_t* src, uint8_t* slot, uint32_t* ndest, uint32_t* count) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const rp::Snap& s = S(before);
+        RP_REQUIRE(n == 0 || hashes, "handoff_hashes: null hash buffer");
+        host_handoff(r, s, nullptr, nullptr, 0, hashes, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot,
+                     ndest, count);
     });
 }
 

@@ -272,6 +272,31 @@ HashRing.prototype.movedNames = function movedNames(keys, moved, n) {
     return out;
 };
 
+// What to do after ringChanged: handoffPlan(keys, snap, n, whoami) gives the transfers that bring
+// every key's lookupN(key, n) servers up to date, grouped by destination, in one device call:
+// {count, dests, groupOff, keyIdx, src, slot} (typed arrays; group g is entries
+// groupOff[g] .. groupOff[g+1] of keyIdx / src / slot; dests ascending by id; src is the first
+// holder before the change that is still in the ring, 0xFFFFFFFF = none, the key is an orphan).
+// whoami (a server name): only what that server has to send. handoffNames() turns the plan into
+// [{dest, transfers: [{key, src (name or null)}]}].
+HashRing.prototype.handoffPlan = function handoffPlan(keys, snap, n, whoami) {
+    n = n === undefined ? 1 : n | 0;
+    return native.ringHandoff(this._h, this._customHash ? this._hashes(keys) : keys, snap._h, n,
+        whoami === undefined ? null : whoami);
+};
+
+HashRing.prototype.handoffNames = function handoffNames(keys, plan) {
+    var out = new Array(plan.dests.length);
+    for (var g = 0; g < out.length; g++) {
+        var t = [];
+        for (var j = plan.groupOff[g]; j < plan.groupOff[g + 1]; j++) {
+            t.push({key: keys[plan.keyIdx[j]], src: plan.src[j] === 0xFFFFFFFF ? null : this.ownerName(plan.src[j])});
+        }
+        out[g] = {dest: this.ownerName(plan.dests[g]), transfers: t};
+    }
+    return out;
+};
+
 // Range hand-off, and planning a change before any key exists: movedRanges(snap, n) gives the hash
 // intervals [lo, hi] (inclusive, ascending, maximal runs of one pair of rows) on which lookupN(h, n)
 // differs between the snapshot and the ring now, in one device pass over the two token sets and

@@ -627,6 +627,99 @@ static napi_value js_ring_moved_keys(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* ringHandoff(h, keys[] | Uint32Array hashes, snap, n, whoami | null) -> {count, dests, groupOff,
+ * keyIdx, src: Uint32Array, slot: Uint8Array}: the transfers that bring every key's lookupN(key, n)
+ * row up to date from its row under the snapshot, grouped by destination id (ascending)
+ * (rp_ring_handoff / _hashes). whoami (a server name): only what that server has to send; a name
+ * the ring never saw sends nothing. */
+static napi_value js_ring_handoff(napi_env env, napi_callback_info info) {
+    ARGS(5);
+    handle_t *h = get_handle(env, argv[0], 1);
+    if (!h) return NULL;
+    handle_t *sh = get_handle(env, argv[2], 4);
+    if (!sh) return NULL;
+    rp_ring *r = (rp_ring *)h->p;
+    const rp_ring_snap *snap = (const rp_ring_snap *)sh->p;
+    int32_t nrep = 0;
+    NAPI_OK(napi_get_value_int32(env, argv[3], &nrep));
+    uint32_t only = RP_NULL_ID;
+    bool nobody = false;
+    napi_valuetype wt;
+    NAPI_OK(napi_typeof(env, argv[4], &wt));
+    if (wt != napi_undefined && wt != napi_null) {
+        napi_value str;
+        NAPI_OK(napi_coerce_to_string(env, argv[4], &str));
+        size_t len = 0;
+        napi_get_value_string_utf8(env, str, NULL, 0, &len);
+        char *buf = (char *)malloc(len + 1);
+        napi_get_value_string_utf8(env, str, buf, len + 1, &len);
+        int rc = rp_ring_server_id(r, buf, (uint32_t)len, &only);
+        free(buf);
+        RP_OK(rc);
+        nobody = only == RP_NULL_ID;
+    }
+    uint32_t bound = 0;
+    RP_OK(rp_ring_id_bound(r, &bound));
+    bool is_typed = false;
+    napi_is_typedarray(env, argv[1], &is_typed);
+    size_t n = 0;
+    void *hv = NULL;
+    strpack_t keys;
+    memset(&keys, 0, sizeof(keys));
+    if (is_typed) {
+        if (typed_get(env, argv[1], napi_uint32_array, &hv, &n)) {
+            napi_throw_type_error(env, NULL, "hashes must be a Uint32Array");
+            return NULL;
+        }
+    } else {
+        if (strpack_from_array(env, argv[1], &keys)) return NULL;
+        n = keys.n;
+    }
+    if (nobody) n = 0;
+    const size_t w = nrep > 1 ? (size_t)nrep : 1u;
+    const size_t cap = n * w < 0xFFFFFFFFu ? n * w : 0xFFFFFFFFu, c1 = cap ? cap : 1;
+    const size_t nd = cap < bound ? cap : bound;
+    uint32_t *dests = (uint32_t *)malloc(4 * (nd + 1)), *goff = (uint32_t *)malloc(4 * (nd + 1)),
+             *kidx = (uint32_t *)malloc(4 * c1), *src = (uint32_t *)malloc(4 * c1);
+    uint8_t *slot = (uint8_t *)malloc(c1);
+    uint32_t count = 0, ndest = 0;
+    int rc = is_typed ? rp_ring_handoff_hashes(r, snap, (const uint32_t *)hv, n, nrep, only, (uint32_t)cap, dests, goff,
+                                               kidx, src, slot, &ndest, &count)
+                      : rp_ring_handoff(r, snap, keys.bytes, keys.off64, 0, n, nrep, only, (uint32_t)cap, dests, goff,
+                                        kidx, src, slot, &ndest, &count);
+    if (!is_typed) strpack_free(&keys);
+    napi_value out = NULL;
+    if (!rc) {
+        void *dd = NULL, *dg = NULL, *dk = NULL, *ds = NULL, *dq = NULL;
+        napi_value vd = new_typed(env, napi_uint32_array, ndest, 4, &dd);
+        napi_value vg = new_typed(env, napi_uint32_array, (size_t)ndest + 1, 4, &dg);
+        napi_value vk = new_typed(env, napi_uint32_array, count, 4, &dk);
+        napi_value vs = new_typed(env, napi_uint32_array, count, 4, &ds);
+        napi_value vq = new_typed(env, napi_uint8_array, count, 1, &dq);
+        if (ndest) memcpy(dd, dests, 4 * (size_t)ndest);
+        memcpy(dg, goff, 4 * ((size_t)ndest + 1));
+        if (count) {
+            memcpy(dk, kidx, 4 * (size_t)count);
+            memcpy(ds, src, 4 * (size_t)count);
+            memcpy(dq, slot, (size_t)count);
+        }
+        napi_create_object(env, &out);
+        napi_set_named_property(env, out, "count", make_u32(env, count));
+        napi_set_named_property(env, out, "dests", vd);
+        napi_set_named_property(env, out, "groupOff", vg);
+        napi_set_named_property(env, out, "keyIdx", vk);
+        napi_set_named_property(env, out, "src", vs);
+        napi_set_named_property(env, out, "slot", vq);
+    }
+    free(dests);
+    free(goff);
+    free(kidx);
+    free(src);
+    free(slot);
+    RP_OK(rc);
+    return out;
+}
+
 /* The servers now in the ring (rp_ring_servers order) as {names: [..], counts: Float64Array}:
  * counts[i * w + q] = table[ids[i] * w + q]. Counts are Numbers: exact below 2^53. */
 static napi_value ring_named_counts(napi_env env, rp_ring *r, const uint64_t *table, size_t w) {
@@ -1538,6 +1631,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringSnapshot", NULL, js_ring_snapshot, NULL, NULL, NULL, napi_default, NULL},
         {"ringSnapInfo", NULL, js_ring_snap_info, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedKeys", NULL, js_ring_moved_keys, NULL, NULL, NULL, napi_default, NULL},
+        {"ringHandoff", NULL, js_ring_handoff, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerLoad", NULL, js_ring_owner_load, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerShare", NULL, js_ring_owner_share, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedRanges", NULL, js_ring_moved_ranges, NULL, NULL, NULL, napi_default, NULL},
