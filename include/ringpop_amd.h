@@ -636,16 +636,21 @@ int rp_sim_join_exchange_local(rp_sim *const *shards, uint32_t nshards);
  *                  incarnation) (lib/membership/index.js:191-195), as the convergence scenarios
  *                  send it (benchmarks/convergence-time/scenarios/); its LocalMemberLeaveEvent
  *                  stops the node's gossip loop and suspicion (on_membership_event.js:32-40). A
- *                  node that is down, or left already, ignores it.
+ *                  node that is down ignores it, and so does one whose own status is `leave`
+ *                  (a node that left and then refuted a suspicion is alive and leaves again).
  *   RP_SIM_JOIN    a fresh process for the node bootstraps into the running cluster
- *                  (index.js:240-322): makeAlive(self, Date.now()); three live nodes (JOIN
- *                  Philox stream over the live nodes in id order) answer the join
+ *                  (index.js:240-322): makeAlive(self, Date.now()); three live nodes, or the one
+ *                  or two there are (JOIN Philox stream over the live nodes in id order), answer
+ *                  the join
  *                  (server/protocol/join.js:126-133: makeAlive(joiner), fullSync);
  *                  mergeJoinResponses (join-response-merge.js:40-56) is stashed and set()
  *                  (index.js:208-247) builds the view, the set handler
  *                  (on_membership_event.js:42-67) fills the ring and the suspicion timers; the
- *                  dissemination is cleared as at bootstrap, then gossip.start shuffles. Needs an
- *                  unsharded handle and one live node besides the joiner.
+ *                  dissemination is cleared as at bootstrap, then gossip.start shuffles. Needs one
+ *                  live node besides the joiner: with nobody to answer, the reference's join
+ *                  never completes, and the step (or rp_sim_join_export) that reaches the event
+ *                  fails with RP_EINVAL. A sharded handle takes joins through rp_sim_join_export /
+ *                  rp_sim_join_import.
  * Convergence then reads: every node that is up and has not left holds the same checksum, each
  * member that left is `leave` and each other member that is down `faulty` in those views.
  * dead[] = down from the start (never started gossip; gossip/index.js:97 never shuffled). */

@@ -725,13 +725,16 @@ void orc_sim_free(orc_sim *s) {
  * ringChanged (maxPiggybackCount stays at the one-server value of makeAlive(self)) and starts a
  * suspicion timer per suspect member. The dissemination is cleared as at bootstrap; gossip.start
  * shuffles. */
-static void node_join(orc_sim *s, uint32_t v, wctx *c) {
+static int node_join(orc_sim *s, uint32_t v, wctx *c) {
     const uint32_t N = s->N;
     const int64_t now = s->now0 + 200 * s->round;
     uint32_t len = 0;
     for (uint32_t u = 0; u < N; u++)
         if (u != v && !s->down[u]) c->cand[len++] = u;
     const uint32_t nj = len < 3 ? len : 3;
+    /* nobody to answer: the reference's join never completes; the model refuses the event (the
+     * device does too), leaving the state untouched */
+    if (!nj) return -2;
     uint32_t resp[3];
     for (uint32_t q = 0; q < nj; q++) {
         uint32_t r = philox_u32(s->seed, TAG_JOIN, (uint32_t)s->round, q, v);
@@ -744,14 +747,9 @@ static void node_join(orc_sim *s, uint32_t v, wctx *c) {
     /* the members array: self, then the first response's order without self */
     uint32_t *base = nd->base ? nd->base : (uint32_t *)malloc(4ull * N);
     base[0] = v;
-    if (nj) {
-        const uint32_t *p0 = perm_full(s, resp[0], &s->nodes[resp[0]], c);
-        for (uint32_t k = 0, o = 1; k < N; k++)
-            if (p0[k] != v) base[o++] = p0[k];
-    } else {
-        for (uint32_t k = 0, o = 1; k < N; k++)
-            if (k != v) base[o++] = k;
-    }
+    const uint32_t *p0 = perm_full(s, resp[0], &s->nodes[resp[0]], c);
+    for (uint32_t k = 0, o = 1; k < N; k++)
+        if (p0[k] != v) base[o++] = p0[k];
     /* the rows: a fresh sparse view, then every member some response holds off its base state */
     nd->ne = 0;
     if (nd->ixcap) memset(nd->ix, 0, 4ull * nd->ixcap);
@@ -797,6 +795,7 @@ static void node_join(orc_sim *s, uint32_t v, wctx *c) {
     s->stopped[v] = 0;
     s->left[v] = 0;
     node_shuffle(s, v, nd, c); /* gossip.start */
+    return 0;
 }
 
 /* Scenario events, applied before the next round (see the header). */
@@ -805,7 +804,7 @@ int orc_sim_event(orc_sim *s, int kind, uint32_t v) {
     switch (kind) {
     case ORC_SIM_KILL: s->down[v] = 1; return 0;
     case ORC_SIM_REVIVE: s->down[v] = 0; return 0;
-    case ORC_SIM_JOIN: node_join(s, v, &s->ctx[0]); return 0;
+    case ORC_SIM_JOIN: return node_join(s, v, &s->ctx[0]);
     case ORC_SIM_LEAVE: {
         node *nd = &s->nodes[v];
         /* the admin handler refuses a redundant leave (server/admin/member.js:84-89); a node that

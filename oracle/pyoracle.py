@@ -344,7 +344,12 @@ class Sim:
         r = self.round
         for er, k, v in self.events:
             if er == r:
-                lib().orc_sim_event(self.h, k, v)
+                rc = lib().orc_sim_event(self.h, k, v)
+                if rc == -2:
+                    raise ValueError("sim: a join needs at least one live node to answer it "
+                                     "(round %d, node %d)" % (r, v))
+                if rc:
+                    raise ValueError("sim: bad event (%d, %d, %d)" % (r, k, v))
         lib().orc_sim_step(self.h)
 
     @property

@@ -2778,8 +2778,10 @@ __global__ __launch_bounds__(kT) void k_phase_d1(SimDev S, const uint32_t* __res
             S.ck_snap[lv] = S.checksum[lv];
             S.inc_snap[lv] = S.inc[row + v];
         }
-        // three issueAsSender() calls; records carry the count after the first one (aux); leg k
-        // carries the records whose count after the first issue + k <= maxPiggybackCount
+        // one issueAsSender() call per helper drawn (three, fewer when fewer members are
+        // pingable); records carry the count after the first one (aux); leg k carries the records
+        // whose count after the first issue + k <= maxPiggybackCount
+        const uint32_t nh = ncand;
         const uint32_t maxp = S.max_piggy[lv];
         const uint32_t nc = S.n_chg[lv];
         Change* chg = S.chg + (uint64_t)lv * S.Cd;
@@ -2795,9 +2797,9 @@ __global__ __launch_bounds__(kT) void k_phase_d1(SimDev S, const uint32_t* __res
                 c1 = c.cnt + 1;
                 if (c1 <= maxp) {
                     emit = true;
-                    if (c.cnt + 3 <= maxp) {
+                    if (c.cnt + nh <= maxp) {
                         keep = true;
-                        c.cnt += 3;
+                        c.cnt += nh;
                     }
                 }
             }
@@ -3977,9 +3979,14 @@ struct Sim {
                 const uint8_t dv = e.kind == RP_SIM_KILL ? 1 : 0;
                 down_changed |= h_dead[e.node] != dv;
                 h_dead[e.node] = dv;
-            } else if (!h_dead[e.node] && !h_left[e.node]) {
+            } else if (!h_dead[e.node]) {
+                // k_leave refuses a redundant leave by the node's own status: a node that left and
+                // then refuted a suspicion is alive again and may leave once more (h_left only
+                // says what convergence expects of it)
                 h_left[e.node] = 1;
-                if (e.node >= v0 && e.node < v0 + NL) leaves.push_back(e.node - v0);
+                const uint32_t lv = e.node - v0;
+                if (local_node(e.node) && std::find(leaves.begin(), leaves.end(), lv) == leaves.end())
+                    leaves.push_back(lv);
             }
             conv_dirty = true;
         }

@@ -1,7 +1,7 @@
 """Regenerate the committed golden fixtures under tests/golden/ by running the REFERENCE
 JavaScript in this container (needs /root/reference and node; never runs on the GPU box).
 
-    python tests/golden/make_golden.py [ring]
+    python tests/golden/make_golden.py [ring] [membership] [sim] [simtiny]
 
 Inputs are built with the oracle's Philox / uuid stream (oracle/pyoracle.py); the reference's
 `farmhash` dependency is served by the oracle's N-API restatement (oracle/gen/farmhash_napi.c),
@@ -20,7 +20,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF = os.environ.get("RINGPOP_REFERENCE", "/root/reference")
 sys.path.insert(0, os.path.join(REPO, "oracle"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
 import pyoracle  # noqa: E402
+import sim_tiny_cases as tiny  # noqa: E402
 
 
 def run_node(script, cases):
@@ -306,6 +308,74 @@ def sim_cases():
     return cases
 
 
+BRANCHES = ("noTarget", "pingReq0", "pingReq1", "pingReq2", "helperDown", "join1", "join2", "leaveRedundant")
+
+
+def runs(rows):
+    """[[count, row], ...]: a row equal to the previous round's is stored once (a settled cluster
+    repeats its rows); tests/golden_util.py load_sim() expands them again."""
+    out = []
+    for r in rows:
+        if out and out[-1][1] == r:
+            out[-1][0] += 1
+        else:
+            out.append([1, r])
+    return out
+
+
+def sim_tiny_cases():
+    """Clusters of 2..17 nodes (tests/sim_tiny_cases.py): the structured families, then 40 seeded
+    random event lists. Final views of every node when n <= 8, else of 0, n-1 and the joiners."""
+    S = synth()
+    cases = []
+    structured = tiny.structured_cases()
+    fams = [(101 + i, "structured", c) for i, c in enumerate(structured)]
+    fams += [(1000 + i, "random", c) for i, c in enumerate(tiny.random_cases())]
+    for seed, family, (name, n, dead, rounds, susp, events) in fams:
+        joiners = sorted({e[2] for e in events if e[1] == "join"} - {0, n - 1})
+        cases.append({"name": name, "family": family, "names": [S.c2_addr(i) for i in range(n)],
+                      "inc0": [int(x) for x in S.c3_members(n)[2]], "dead": dead, "seed": seed,
+                      "suspRounds": susp, "now0": S.NOW0, "rounds": rounds,
+                      "views": list(range(n)) if n <= 8 else [0, n - 1] + joiners, "events": events})
+    return cases
+
+
+def make_sim_tiny():
+    cases = sim_tiny_cases()
+    outs = run_node("ref_sim.js", cases)
+    fixture = {"generator": "tests/golden/make_golden.py simtiny + tests/sim_tiny_cases.py + tests/golden/ref_sim.js",
+               "reference": "as sim_golden.json",
+               "note": "the schema of sim_golden.json once loaded through tests/golden_util.py load_sim(): "
+                       "checksums and maxPiggyback are stored as checksumRuns / maxPiggybackRuns = [[count, row], "
+                       "...], count consecutive rounds with that row; plus per case: family (structured | random) "
+                       "and branches = how often the reference took each small-cluster branch (no ping target, "
+                       "ping-req with 0 / 1 / 2 helpers, a helper that is down, a join answered by 1 / 2 "
+                       "nodes, a leave refused as redundant)",
+               "cases": []}
+    total = dict.fromkeys(BRANCHES, 0)
+    for c, o in zip(cases, outs):
+        f = {k: c[k] for k in ("name", "family", "seed", "suspRounds", "now0", "rounds", "views")}
+        f["n"] = len(c["names"])
+        f["dead"] = c["dead"]
+        f["events"] = c["events"]
+        f["branches"] = {k: o["branches"][k] for k in BRANCHES}
+        for k in BRANCHES:
+            total[k] += o["branches"][k]
+        f["checksumRuns"] = runs(o["rounds"])
+        f["maxPiggybackRuns"] = runs(o["maxPiggyback"])
+        f["fullSyncs"] = o["fullSyncs"]
+        f["finalViews"] = o["finalViews"]
+        fixture["cases"].append(f)
+    print("branches taken:", total)
+    # the fixture exists for these branches: a counter at zero means a case has to be added
+    assert all(total[k] > 0 for k in BRANCHES), total
+    path = os.path.join(HERE, "sim_tiny_golden.json")
+    with open(path, "w") as fh:
+        json.dump(fixture, fh, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < 300_000
+
+
 def make_sim():
     cases = sim_cases()
     outs = run_node("ref_sim.js", cases)
@@ -343,3 +413,5 @@ if __name__ == "__main__":
         make_membership()
     if "sim" in what:
         make_sim()
+    if "simtiny" in what:
+        make_sim_tiny()

@@ -153,6 +153,10 @@ input.cases.forEach(function (c) {
     var down = dead.slice();
     function live(v) { return !down[v]; }
     var co = {name: c.name, rounds: [], maxPiggyback: []};
+    // how often the case took each small-cluster branch (tests/golden/sim_tiny_golden.json)
+    var br = {noTarget: 0, pingReq0: 0, pingReq1: 0, pingReq2: 0, helperDown: 0, join1: 0, join2: 0,
+        leaveRedundant: 0};
+    co.branches = br;
     for (round = 0; round < c.rounds; round++) {
         (c.events || []).forEach(function (e) {
             if (e[0] !== round) { return; }
@@ -170,6 +174,10 @@ input.cases.forEach(function (c) {
                 var cands = [];
                 for (var u = 0; u < N; u++) { if (u !== v && live(u)) { cands.push(u); } }
                 var nj = Math.min(3, cands.length);
+                // nobody to answer: the reference's join never completes (join-sender.js keeps
+                // retrying); the model refuses the event, as the oracle and the device do
+                if (nj === 0) { throw new Error(c.name + ': a join needs at least one live node to answer it'); }
+                if (nj < 3) { br['join' + nj]++; }
                 for (var q = 0; q < nj; q++) {
                     var jj = q + scaled(philox([round, q, v, 0], [seed, TAG_JOIN])[0], cands.length - q);
                     var tt = cands[q]; cands[q] = cands[jj]; cands[jj] = tt;
@@ -191,7 +199,7 @@ input.cases.forEach(function (c) {
                 var lm = nodes[v].membership.localMember;
                 if (live(v) && lm.status !== 'leave') {
                     nodes[v].membership.makeLeave(c.names[v], lm.incarnationNumber);
-                }
+                } else if (live(v)) { br.leaveRedundant++; }
             }
         });
         var target = [], ping = [], resp = [];
@@ -200,7 +208,7 @@ input.cases.forEach(function (c) {
             target[v] = -1;
             if (!live(v) || nodes[v].gossip.isStopped) { continue; }
             var t = nodes[v].memberIterator.next();
-            if (!t) { continue; }
+            if (!t) { br.noTarget++; continue; }  // no member is pingable
             target[v] = idOf[t.address];
             var m = nodes[v].membership;
             ping[v] = wire({checksum: m.checksum, changes: nodes[v].dissemination.issueAsSender(),
@@ -230,6 +238,7 @@ input.cases.forEach(function (c) {
             m = nodes[v].membership;
             var tm = m.findMemberByAddress(c.names[j]);
             var hs = m.getRandomPingableMembers(3, [tm.address]);
+            if (hs.length < 3) { br['pingReq' + hs.length]++; }
             if (hs.length === 0) { m.makeSuspect(tm.address, tm.incarnationNumber); continue; }
             helpers[v] = hs.map(function (x) { return idOf[x.address]; });
             legs[v] = hs.map(function () {
@@ -243,7 +252,7 @@ input.cases.forEach(function (c) {
             lresp[v] = [];
             for (var k = 0; k < helpers[v].length; k++) {
                 var h = helpers[v][k];
-                if (!live(h)) { lresp[v][k] = null; continue; }
+                if (!live(h)) { br.helperDown++; lresp[v][k] = null; continue; }
                 var body = legs[v][k];
                 nodes[h].membership.update(body.changes);
                 nodes[h].dissemination.issueAsSender();  // the helper's own ping of the dead target

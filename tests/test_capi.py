@@ -1,5 +1,6 @@
 """CPU tests of the C ABI: librpamd.so builds, loads without a GPU, exports every symbol the
 public header declares, and its host farmhash32 agrees with the oracle (no device calls)."""
+import ctypes
 import os
 import random
 import re
@@ -46,3 +47,19 @@ def test_host_farmhash_replica_strings(rpa, orc):
     for s in ["10.28.5.35:20800", "127.0.0.1:3000", "test 1"]:
         for i in range(120):
             assert rpa.hash32(s + str(i)) == orc.hash32(s + str(i))
+
+
+def test_sim_create_refuses_one_node(rpa):
+    """The simulator's smallest cluster is two nodes: n = 1 (and 0) is RP_EINVAL before any
+    device call, and no handle comes back."""
+    names = b"127.0.0.1:3000"
+    off = np.array([0, len(names)], dtype=np.uint32)
+    inc0 = np.array([1], dtype=np.int64)
+    dead = np.zeros(1, dtype=np.uint8)
+    for n in (1, 0):
+        h = ctypes.c_void_p()
+        rc = rpa.lib().rp_sim_create(n, names, off.ctypes.data, inc0.ctypes.data, dead.ctypes.data, 1, 3, 0, 0,
+                                     ctypes.byref(h))
+        assert rc == -1  # RP_EINVAL
+        assert b"sim_create" in rpa.lib().rp_last_error()
+        assert not h.value

@@ -54,7 +54,10 @@ def test_js_gossipsim_matches_reference_goldens(gpu, tmp_path):
     spec.loader.exec_module(S)
     cases = []
     golden = gu.load("sim_golden.json")["cases"]
-    for c in golden[:2] + [x for x in golden if x["name"] in ("n24-revive", "n30-join")]:
+    tiny = [x for x in gu.load_sim("sim_tiny_golden.json")["cases"]
+            if x["name"] in ("n2-killrevive", "n3-two-responders", "n5-all-leave")]
+    assert len(tiny) == 3
+    for c in golden[:2] + [x for x in golden if x["name"] in ("n24-revive", "n30-join")] + tiny:
         n = c["n"]
         cases.append(dict(c, names=[S.c2_addr(i) for i in range(n)], inc0=[int(x) for x in S.c3_members(n)[2]]))
     res = run_node("sim_parity.js", {"cases": cases}, tmp_path)
