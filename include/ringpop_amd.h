@@ -325,6 +325,59 @@ int rp_ring_handoff_hashes(rp_ring *r, const rp_ring_snap *before, const uint32_
                            uint32_t *dests, uint32_t *group_off, uint32_t *key_idx, uint32_t *src,
                            uint8_t *slot, uint32_t *ndest, uint32_t *count);
 
+/* Routing agreement: every key's owner under many views of one ring at once (what handleOrProxy
+ * does with ring.lookup(key) on nodes whose rings differ while gossip spreads). r is the base
+ * ring: it holds every server. A view allows a subset of its servers. For a key hash h let i be
+ * the position of the first token >= h, wrapping to 0, as lookup finds it
+ * (lib/ring/index.js:145-154). Then
+ *   owner(v, h)  the owner of the first token in i, i + 1, ... (cyclic, at most every token once)
+ *                whose server view v allows; RP_NULL_ID if there is none.
+ * That is lookup on a ring holding exactly the view's servers as long as no two servers' replica
+ * tokens collide. Where tokens collide (about 108 of 10^6 at 10,000 servers) the answer is
+ * defined by this walk over r's arrays; the reference's insert-if-absent / erase-by-key rings
+ * depend on their history there. lookup only (n = 1).
+ * Inputs:
+ *   keys         d_keys with d_off / stride as for rp_ring_lookup_dev, or d_hashes (a caller
+ *                hashFunc's key hashes): exactly one of d_keys and d_hashes is given
+ *   views        server id is allowed in view v when it has a token in r, col = d_col[id] is not
+ *                RP_NULL_ID, and d_rows[v * row_stride + col] & bit is non-zero. d_col NULL:
+ *                col = id, and then row_stride >= id_cap. A col at or past row_stride counts as
+ *                RP_NULL_ID. d_col has id_cap entries; id_cap >= rp_ring_id_bound, else RP_EINVAL.
+ *   d_truth      one more view, the truth: d_truth[col] & bit. NULL: every server of r. t(k) is
+ *                key k's owner under the truth.
+ *   d_active     d_active[v] != 0 marks the views that are counted. NULL: all.
+ * Outputs, each nullable:
+ *   wrong[v]         keys with owner(v, k) != t(k)
+ *   lost[v]          keys whose owner(v, k) is not null and is not allowed by the truth (requests
+ *                    sent to a server that is gone); lost[v] <= wrong[v]
+ *                    Both are uint64[n_views]. accumulate != 0 adds to what they hold, otherwise
+ *                    they are set; inactive views get 0 (are left alone under accumulate).
+ *   key_wrong[k]     active views with owner(v, k) != t(k)
+ *   truth_owner[k]   t(k)
+ *   owners[k * n_views + v]  owner(v, k) of every view, active or not (the diagnostic output:
+ *                    4 * n * n_views bytes)
+ * n == 0 and n_views == 0 are not errors. The planes (n_views bits per server id) live in a
+ * scratch the ring owns, allocated when it first grows, never per call after that. A view that
+ * allows S_v of S servers costs about S / S_v walk steps per key, in that view's word only: a
+ * view with one server out of thousands walks up to every token per key. The _dev form is
+ * stream-ordered and never syncs with the host, except that a stream other than the ring's own
+ * first waits for the ring's pending rebuilds (as rp_ring_lookupn_dev does). The host form takes
+ * host buffers (truth: row_stride bytes) and is synchronous. */
+int rp_ring_route_views_dev(rp_ring *r, const uint8_t *d_keys, const uint64_t *d_off, uint32_t stride,
+                            const uint32_t *d_hashes, uint64_t n,
+                            const uint8_t *d_rows, uint64_t row_stride, uint8_t bit, uint32_t n_views,
+                            const uint32_t *d_col, uint32_t id_cap,
+                            const uint8_t *d_truth, const uint8_t *d_active, int accumulate,
+                            uint64_t *d_wrong, uint64_t *d_lost, uint32_t *d_key_wrong,
+                            uint32_t *d_truth_owner, uint32_t *d_owners, void *stream);
+int rp_ring_route_views(rp_ring *r, const char *keys, const uint64_t *off, uint32_t stride,
+                        const uint32_t *hashes, uint64_t n,
+                        const uint8_t *rows, uint64_t row_stride, uint8_t bit, uint32_t n_views,
+                        const uint32_t *col, uint32_t id_cap,
+                        const uint8_t *truth, const uint8_t *active, int accumulate,
+                        uint64_t *wrong, uint64_t *lost, uint32_t *key_wrong,
+                        uint32_t *truth_owner, uint32_t *owners);
+
 /* ------------------------------------------------------------------ Membership
  * Replaces the hot path of lib/membership/index.js Membership: update (249-324) with the
  * Member.evaluateUpdate rules (lib/membership/member.js:71-202) and computeChecksum /
@@ -668,6 +721,24 @@ int rp_sim_piggyback(rp_sim *s, uint32_t *out);
  * records sent, views hashed, bytes of the all-alive checksum string (a view's string length
  * within a few bytes per deviated member)}. */
 int rp_sim_counters(rp_sim *s, uint64_t *out8);
+/* Node v's ring membership: in_ring[N] 0/1, what its ring holds (kept by the alive / faulty /
+ * leave handler and the join's set handler, lib/on_membership_event.js). */
+int rp_sim_ring_members(rp_sim *s, uint32_t v, uint8_t *in_ring);
+/* Routing agreement of the handle's nodes: rp_ring_route_views_dev on the handle's stream, after
+ * the rounds queued so far, with every local node's ring membership as one view of `ring`. ring
+ * holds the members as servers, matched by name (a member the ring lacks is allowed nowhere; the
+ * map is cached per ring handle and id bound) and lives on the handle's device, else RP_EINVAL.
+ * truth[a] != 0: member a really serves; node v is counted when truth[v] != 0. truth NULL on an
+ * unsharded handle: the node is up (neither dead[] nor killed by the scenario so far) and its
+ * own status in its own view is not `leave`. A sharded handle needs truth (RP_EINVAL otherwise)
+ * and routes only at a round boundary (before stage 0). Host buffers, synchronous; outputs as
+ * rp_ring_route_views documents them, each nullable: wrong / lost [the handle's nodes],
+ * key_wrong / truth_owner [n] (truth_owner: ring ids). */
+int rp_sim_routing(rp_sim *s, rp_ring *ring, const char *keys, const uint64_t *off, uint32_t stride, uint64_t n,
+                   const uint8_t *truth, uint64_t *wrong, uint64_t *lost, uint32_t *key_wrong,
+                   uint32_t *truth_owner);
+int rp_sim_routing_hashes(rp_sim *s, rp_ring *ring, const uint32_t *hashes, uint64_t n, const uint8_t *truth,
+                          uint64_t *wrong, uint64_t *lost, uint32_t *key_wrong, uint32_t *truth_owner);
 
 /* Stream-ordered copy between any host / device buffers (hipMemcpyDefault); NULL stream =
  * synchronous. Used by hosts that move sharded-simulator messages. */

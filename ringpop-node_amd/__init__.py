@@ -93,6 +93,10 @@ SIGNATURES = {
     "rp_ring_handoff_dev": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rp_ring_handoff": (_INT, [_P, _P, _P, _P, _U32, _U64, _I32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
     "rp_ring_handoff_hashes": (_INT, [_P, _P, _P, _U64, _I32, _U32, _U32, _P, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_route_views_dev": (_INT, [_P, _P, _P, _U32, _P, _U64, _P, _U64, ctypes.c_uint8, _U32, _P, _U32, _P, _P,
+                                       _INT, _P, _P, _P, _P, _P, _P]),
+    "rp_ring_route_views": (_INT, [_P, _P, _P, _U32, _P, _U64, _P, _U64, ctypes.c_uint8, _U32, _P, _U32, _P, _P, _INT,
+                                   _P, _P, _P, _P, _P]),
     "rp_members_create": (_INT, [_U32, _INT, _P]),
     "rp_members_destroy": (_INT, [_P]),
     "rp_members_intern": (_INT, [_P, _P, _P, _U32, _P]),
@@ -144,6 +148,9 @@ SIGNATURES = {
     "rp_wire_decode_dev": (_INT, [_P, _P, _P, _U32, _P, _U32, _P, _P, _P, _P]),
     "rp_wire_decode": (_INT, [_P, _P, _P, _U32, _P, _U32, _P, _P, _P]),
     "rp_sim_counters": (_INT, [_P, _P]),
+    "rp_sim_ring_members": (_INT, [_P, _U32, _P]),
+    "rp_sim_routing": (_INT, [_P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P, _P]),
+    "rp_sim_routing_hashes": (_INT, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "rp_members_defer_checksum": (_INT, [_P, _INT]),
     "rp_members_checksum_shard": (_INT, [_P, _U32, _U32, _U32]),
     "rp_members_checksum_history": (_INT, [_P, _P, _P, _U32, _P]),
@@ -604,6 +611,94 @@ class HashRing:
         check(lib().rp_ring_handoff_dev(self._h, before._h, keys_ptr, off_ptr, stride, n, nrep, only_src, cap,
                                         dests_ptr, goff_ptr, key_idx_ptr, src_ptr, slot_ptr, ndest_ptr, count_ptr,
                                         stream))
+
+    # -- routing agreement (key owners under many views of this ring at once)
+    def route_views_dev(self, n, rows_ptr, row_stride, n_views, keys_ptr=None, hashes_ptr=None, bit=1, col_ptr=None,
+                        id_cap=None, truth_ptr=None, active_ptr=None, accumulate=False, wrong_ptr=None, lost_ptr=None,
+                        key_wrong_ptr=None, truth_owner_ptr=None, owners_ptr=None, stride=36, off_ptr=None,
+                        stream=None):
+        """rp_ring_route_views_dev on device buffers: keys_ptr (with stride / off_ptr) or hashes_ptr."""
+        check(lib().rp_ring_route_views_dev(self._h, keys_ptr, off_ptr, stride, hashes_ptr, n, rows_ptr, row_stride,
+                                            bit, n_views, col_ptr, self.id_bound() if id_cap is None else id_cap,
+                                            truth_ptr, active_ptr, int(bool(accumulate)), wrong_ptr, lost_ptr,
+                                            key_wrong_ptr, truth_owner_ptr, owners_ptr, stream))
+
+    def _route(self, blob, off, stride, hs, k, allowed, truth, active, col, owners):
+        allowed = np.ascontiguousarray(allowed, dtype=np.uint8)
+        if allowed.ndim != 2:
+            raise ValueError("allowed must be a [views, columns] matrix")
+        if allowed.shape[1] == 0:  # (no column at all: one that allows nobody)
+            allowed = np.zeros((allowed.shape[0], 1), dtype=np.uint8)
+            truth = None if truth is None else np.zeros(1, dtype=np.uint8)
+        nv, rs = allowed.shape
+        cap = self.id_bound()
+        colv = None
+        if col is not None:
+            colv = np.ascontiguousarray(col, dtype=np.uint32)
+            if len(colv) < cap:
+                raise ValueError("col must cover the ring's id bound")
+        tr = None
+        if truth is not None:
+            tr = np.ascontiguousarray(truth, dtype=np.uint8)
+            if len(tr) != rs:
+                raise ValueError("truth must have one entry per column")
+        ac = None
+        if active is not None:
+            ac = np.ascontiguousarray(active, dtype=np.uint8)
+            if len(ac) != nv:
+                raise ValueError("active must have one entry per view")
+        res = {"wrong": np.zeros(nv, dtype=np.uint64), "lost": np.zeros(nv, dtype=np.uint64),
+               "key_wrong": np.zeros(k, dtype=np.uint32), "truth_owner": np.full(k, NULL_ID, dtype=np.uint32)}
+        if owners:
+            res["owners"] = np.full((k, nv), NULL_ID, dtype=np.uint32)
+        check(lib().rp_ring_route_views(self._h, None if hs is not None else blob.ctypes.data, _ptr(off), stride,
+                                        _ptr(hs), k, allowed.ctypes.data if nv else None, rs, 1, nv,
+                                        _ptr(colv), cap, _ptr(tr), _ptr(ac), 0,
+                                        res["wrong"].ctypes.data if nv else None,
+                                        res["lost"].ctypes.data if nv else None,
+                                        res["key_wrong"].ctypes.data if k else None,
+                                        res["truth_owner"].ctypes.data if k else None,
+                                        res["owners"].ctypes.data if owners and k and nv else None))
+        return res
+
+    def route_view_ids(self, keys, allowed, truth=None, active=None, col=None, owners=False):
+        """Key owners under every view at once. allowed[v, c] (bool): view v allows the server of
+        column c; a server id's column is col[id] (NULL_ID: allowed nowhere), or id itself without
+        col. truth[c]: the truth, one more view (None: every server of the ring); active[v]: the views
+        that are counted (None: all). Returns {"wrong": uint64[views] keys whose owner under the view
+        is not the truth's, "lost": uint64[views] keys sent to a server the truth does not allow,
+        "key_wrong": uint32[keys] active views that disagree, "truth_owner": uint32[keys]} and, with
+        owners=True, "owners": uint32[keys, views] (NULL_ID: null)."""
+        if self.hashFunc is not None:
+            return self.route_view_hashes(np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32),
+                                          allowed, truth, active, col, owners)
+        blob, off, stride, k = self._key_pack(keys)
+        return self._route(blob, off, stride, None, k, allowed, truth, active, col, owners)
+
+    def route_view_hashes(self, hashes, allowed, truth=None, active=None, col=None, owners=False):
+        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
+        return self._route(None, None, 0, hs, len(hs), allowed, truth, active, col, owners)
+
+    def routeViews(self, keys, views, truth=None):
+        """views: a list of server-name lists (the servers each view's ring holds); truth: one more
+        (None: every server of this ring). Returns {"owners": per key the owner name under every
+        view (None: null), "truth": per key the owner name under the truth, "wrong" / "lost": per view
+        the key counts of route_view_ids}. Names this ring does not hold are ignored."""
+        keys = [k if isinstance(k, (bytes, np.ndarray)) else str(k) for k in keys]
+        cap = self.id_bound()
+
+        def row(names):
+            r = np.zeros(cap, dtype=np.uint8)
+            for s in names:
+                i = self.server_id(s)
+                if i != NULL_ID:
+                    r[i] = 1
+            return r
+        allowed = np.stack([row(v) for v in views]) if len(views) else np.zeros((0, cap), dtype=np.uint8)
+        res = self.route_view_ids(keys, allowed, truth=None if truth is None else row(truth), owners=True)
+        nm = lambda i: None if i == NULL_ID else self.name(int(i))  # noqa: E731
+        return {"owners": [[nm(i) for i in r] for r in res["owners"]], "truth": [nm(i) for i in res["truth_owner"]],
+                "wrong": [int(x) for x in res["wrong"]], "lost": [int(x) for x in res["lost"]]}
 
     # -- owner load and hash-space share (how even is the ring?)
     def id_bound(self):
@@ -1276,6 +1371,37 @@ class GossipSim:
         check(lib().rp_sim_counters(self._h, out.ctypes.data))
         return dict(zip(_COUNTER_NAMES, (int(x) for x in out)))
 
+    def ring_members(self, v):
+        """Node v's ring membership (bool[N]): the members its ring holds."""
+        out = np.empty(self.N, dtype=np.uint8)
+        check(lib().rp_sim_ring_members(self._h, v, out.ctypes.data))
+        return out.astype(bool)
+
+    def routing(self, ring, keys, truth=None):
+        """Routing agreement of this handle's nodes on `ring` (a HashRing holding the members as
+        servers, on the same device): {"wrong", "lost": uint64 per node, "key_wrong": uint32 per key,
+        "truth_owner": ring ids per key} (HashRing.route_view_ids). truth[a]: member a really serves
+        (None, unsharded handles only: the node is up and has not left)."""
+        nl = getattr(self, "NL", self.N)
+        tr = None if truth is None else np.ascontiguousarray(np.asarray(truth) != 0, dtype=np.uint8)
+        if tr is not None and len(tr) != self.N:
+            raise ValueError("truth must have one entry per member")
+        hs = None
+        if ring.hashFunc is not None:
+            hs = np.array([ring.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
+            k = len(hs)
+        else:
+            blob, off, stride, k = ring._key_pack(keys)
+        res = {"wrong": np.zeros(nl, dtype=np.uint64), "lost": np.zeros(nl, dtype=np.uint64),
+               "key_wrong": np.zeros(k, dtype=np.uint32), "truth_owner": np.full(k, NULL_ID, dtype=np.uint32)}
+        outs = (_ptr(tr), res["wrong"].ctypes.data if nl else None, res["lost"].ctypes.data if nl else None,
+                res["key_wrong"].ctypes.data if k else None, res["truth_owner"].ctypes.data if k else None)
+        if hs is not None:
+            check(lib().rp_sim_routing_hashes(self._h, ring._h, hs.ctypes.data, k, *outs))
+        else:
+            check(lib().rp_sim_routing(self._h, ring._h, blob.ctypes.data, _ptr(off), stride, k, *outs))
+        return res
+
 
 # ---------------------------------------------------------------------------------------------
 # Sharded simulator (C5): nodes partitioned over shards; a round = five stages + four message
@@ -1391,6 +1517,9 @@ class SimShard:
         check(lib().rp_sim_counters(self._h, out.ctypes.data))
         return out
 
+    ring_members = GossipSim.ring_members
+    routing = GossipSim.routing
+
 
 def conv_reduce(parts):
     """Convergence (scenario-runner.js:152-170 + killed members faulty everywhere) from the
@@ -1416,6 +1545,8 @@ class ShardedGossipSim:
                  bounds=None, events=()):
         self.N = len(names)
         self.G = nshards
+        self._dead = np.array(dead, dtype=np.uint8)
+        self._events = [tuple(e) for e in (events or ())]
         devices = devices or [0] * nshards
         self.shards = [SimShard(names, inc0, dead, nshards, g, seed, suspicion_rounds, now0, devices[g], bounds,
                                 events) for g in range(nshards)]
@@ -1471,6 +1602,41 @@ class ShardedGossipSim:
 
     def piggyback(self):
         return np.concatenate([s.piggyback() for s in self.shards])
+
+    def ring_members(self, v):
+        for s in self.shards:
+            if s.v0 <= v < s.v0 + s.NL:
+                return s.ring_members(v)
+        raise IndexError(v)
+
+    def default_truth(self):
+        """bool[N]: the node is up (dead[] and the scenario's kills, revives and joins so far) and
+        its own status in its own view is not `leave` (what rp_sim_routing takes for an unsharded
+        handle's truth), gathered over the shards."""
+        up = ~np.asarray(self._dead, dtype=bool)
+        rnd = self.round
+        for r, k, v in sorted(self._events, key=lambda e: int(e[0])):
+            if int(r) >= rnd:
+                break
+            k = SIM_EVENT.get(k, k)
+            if k == SIM_EVENT["kill"]:
+                up[int(v)] = False
+            elif k in (SIM_EVENT["revive"], SIM_EVENT["join"]):
+                up[int(v)] = True
+        for s in self.shards:
+            for v in range(s.v0, s.v0 + s.NL):
+                if up[v] and s.view(v)[0][v] == STATUS["leave"]:
+                    up[v] = False
+        return up
+
+    def routing(self, ring, keys, truth=None):
+        """GossipSim.routing over the shards: wrong / lost in node order, key_wrong summed."""
+        tr = self.default_truth() if truth is None else np.asarray(truth) != 0
+        parts = [s.routing(ring, keys, tr) for s in self.shards]
+        return {"wrong": np.concatenate([p["wrong"] for p in parts]),
+                "lost": np.concatenate([p["lost"] for p in parts]),
+                "key_wrong": sum((p["key_wrong"] for p in parts[1:]), parts[0]["key_wrong"].copy()),
+                "truth_owner": parts[0]["truth_owner"]}
 
 
 class _DeviceBytes:

@@ -2462,6 +2462,18 @@ struct HandoffScratch {
     void use_on(hipStream_t st) { order.use_on(st); }
 };
 
+// The scratch of the routing-agreement calls of one ring, ordered across streams in the same way.
+struct RouteScratch {
+    DevBuf<unsigned long long> plane;  // [id bound][view words]: the views that allow each server
+    DevBuf<unsigned long long> meta;   // any[view words] | active[view words] | truth allows anybody
+    DevBuf<uint8_t> tr;                // per server id: allowed by the truth
+    DevBuf<uint8_t> io8;               // the host form's rows, truth and active bytes
+    DevBuf<uint32_t> io32;             // the host form's column map and uint32 outputs
+    DevBuf<unsigned long long> io64;   // the host form's wrong | lost
+    StreamOrder order;
+    void use_on(hipStream_t st) { order.use_on(st); }
+};
+
 struct Ring {
     int device = 0;
     hipStream_t st = nullptr;
@@ -2530,6 +2542,7 @@ struct Ring {
     LoadScratch load_ws;  // owner load / share
     RangeScratch range_ws;  // moved ranges
     HandoffScratch handoff_ws;  // hand-off plan
+    RouteScratch route_ws;  // routing agreement
     uint32_t inring_n = 0;  // the ids d_inring covers (ring_compute_checksum copies in_ring at every change)
 
     RingView view() const {
@@ -4260,6 +4273,280 @@ static void host_moved_ranges(const RingView& bv, uint32_t sc_b, const RingView&
     }
 }
 
+// ------------------------------------------------------------- routing agreement
+// Key owners under many views of one base ring at once (rp_ring_route_views*). A view allows a
+// subset of the ring's servers; owner(v, h) is the owner of the first token at or after h's
+// position, walking cyclically, whose server view v allows. Two launches:
+//   k_route_pack  transposes the caller's byte rows rows[v][col[id]] & bit into bit planes
+//                 plane[id][PW] (bit b of word w: view 64 w + b allows server id; tail bits and
+//                 servers without tokens are zero). One thread per (id, word): it reads the 64
+//                 rows' bytes at its column, so a workgroup's 256 consecutive ids read 256
+//                 contiguous bytes of a row per step when col is the identity. It also writes the
+//                 truth byte per id, the active words, any[w] = OR of the planes over the ids
+//                 (views that allow nobody are answered RP_NULL_ID without a walk) and whether the
+//                 truth allows anybody.
+//   k_route       a wave takes 64 keys: each lane hashes one, finds its position (moved_find) and
+//                 walks to its owner under the truth. Then the wave walks the keys one by one with
+//                 one lane per view word: the step's owner is wave-uniform, a lane whose word has
+//                 views left loads plane[owner][word], and the views it answers are classed as
+//                 agreeing, wrong or lost against the truth and leave the word. A repeated owner
+//                 answers nothing new. The first step's owner is read with the position (one
+//                 load a lane, not one a key); after the first step the walk issues four steps'
+//                 plane loads together (the positions are known in advance). Counts go to uint32 LDS
+//                 counters per view (one LDS atomic per wrong view: disagreements are rare) and
+//                 are flushed with 64-bit global atomics; a launch takes fewer than 2^32 keys.
+//                 blockIdx.y is the block of up to 64 view words the workgroup's LDS counts.
+constexpr int kRouteThreads = 512;
+constexpr int kRoutePackThreads = 256;
+constexpr uint32_t kRouteVBlock = 4096;       // views a block (RP_ROUTE_VBLOCK): 64 words, one a lane
+constexpr uint64_t kRouteChunk = 1ull << 31;  // keys a launch: the uint32 LDS counters cannot overflow
+
+__global__ __launch_bounds__(kRoutePackThreads) void k_route_pack(
+    const uint8_t* __restrict__ rows, uint64_t row_stride, uint8_t bit, uint32_t V, const uint32_t* __restrict__ col,
+    uint32_t idb, const uint8_t* __restrict__ inring, uint32_t inring_n, const uint8_t* __restrict__ truth,
+    const uint8_t* __restrict__ active, uint32_t PW, unsigned long long* __restrict__ plane,
+    unsigned long long* __restrict__ any, unsigned long long* __restrict__ act, unsigned long long* __restrict__ tany,
+    uint8_t* __restrict__ tr) {
+    const uint32_t id = blockIdx.x * (uint32_t)kRoutePackThreads + threadIdx.x, w = blockIdx.y, lane = threadIdx.x & 63;
+    const bool inr = id < idb && id < inring_n && inring[id] != 0;
+    uint32_t c = NIL;
+    if (inr) {
+        c = col ? col[id] : id;
+        if ((uint64_t)c >= row_stride) c = NIL;  // (never read past a row)
+    }
+    const uint32_t vb = w * 64u;
+    const uint32_t nv = V > vb ? (V - vb < 64u ? V - vb : 64u) : 0u;
+    unsigned long long word = 0;
+    if (c != NIL) {
+        const uint8_t* p = rows + (uint64_t)vb * row_stride + c;
+#pragma unroll 8
+        for (uint32_t b = 0; b < nv; b++)
+            word |= (unsigned long long)((p[(uint64_t)b * row_stride] & bit) != 0) << b;
+    }
+    if (id < idb) plane[(uint64_t)id * PW + w] = word;
+    unsigned long long r = word;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) r |= __shfl_xor(r, o);
+    if (lane == 0 && r) atomicOr(any + w, r);
+    if (w == 0) {
+        const bool t = truth ? (c != NIL && (truth[c] & bit) != 0) : inr;
+        if (id < idb) tr[id] = t ? 1 : 0;
+        const unsigned long long m = __ballot(t);
+        if (lane == 0 && m) atomicOr(tany, 1ull);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) {
+        const uint32_t v = vb + lane;
+        const unsigned long long m = __ballot(v < V && (active ? active[v] != 0 : true));
+        if (lane == 0) act[w] = m;
+    }
+}
+
+// FIXED: 36-byte keys at stride 36 from a 4-byte aligned base (nine dword loads a lane).
+// OWN: the per-view owners are written (the diagnostic output), and inactive views are walked too.
+template <bool FIXED, bool OWN>
+__global__ __launch_bounds__(kRouteThreads) void k_route(
+    const uint8_t* __restrict__ keys, const uint64_t* __restrict__ off, uint32_t stride,
+    const uint32_t* __restrict__ hashes, uint32_t n, RingView rv, const unsigned long long* __restrict__ plane,
+    const unsigned long long* __restrict__ any, const unsigned long long* __restrict__ act,
+    const unsigned long long* __restrict__ tany, const uint8_t* __restrict__ tr, uint32_t PW, uint32_t V,
+    uint32_t VBW, unsigned long long* __restrict__ wrong, unsigned long long* __restrict__ lost,
+    uint32_t* __restrict__ key_wrong, uint32_t* __restrict__ truth_owner, uint32_t* __restrict__ owners) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_route[];
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t w0 = blockIdx.y * VBW;
+    const uint32_t nw = PW - w0 < VBW ? PW - w0 : VBW;  // this block's view words (<= 64)
+    uint32_t* s_wrong = s_route;
+    uint32_t* s_lost = s_route + nw * 64u;
+    for (uint32_t i = tid; i < nw * 128u; i += kRouteThreads) s_route[i] = 0;
+    __syncthreads();
+    const bool on = lane < nw;
+    const uint32_t w = w0 + (on ? lane : 0u);
+    unsigned long long valid = 0;
+    if (on && V > w * 64u) valid = V - w * 64u >= 64u ? ~0ull : ((1ull << (V - w * 64u)) - 1ull);
+    const unsigned long long actw = on ? act[w] : 0ull;
+    const unsigned long long anyw = on ? any[w] : 0ull;
+    const unsigned long long walked = OWN ? valid : (valid & actw);
+    const bool has_truth = *tany != 0;
+    const uint32_t M = rv.M;
+    const uint32_t step = gridDim.x * (uint32_t)kRouteThreads;
+    for (uint64_t base = ((uint64_t)blockIdx.x * (kRouteThreads / 64) + wave) * 64u; base < n; base += step) {
+        const uint32_t cnt = n - base < 64u ? (uint32_t)(n - base) : 64u;
+        uint32_t pos = 0, tk = NIL, o0 = 0;
+        if (lane < cnt) {
+            const uint64_t k = base + lane;
+            uint32_t h;
+            if constexpr (FIXED) {
+                const uint32_t* s1 = reinterpret_cast<const uint32_t*>(keys + k * 36u);
+                uint32_t kw[9];
+#pragma unroll
+                for (int j = 0; j < 9; j++) kw[j] = s1[j];
+                h = fh::hash32_words<36>(kw);
+            } else if (hashes) {
+                h = hashes[k];
+            } else {
+                uint64_t b, e;
+                if (stride) {
+                    b = k * stride;
+                    e = b + stride;
+                } else {
+                    b = off[k];
+                    e = off[k + 1];
+                }
+                h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
+            }
+            pos = moved_find(rv, h);
+            if (pos >= M) pos = 0;
+            o0 = rv.own[pos];
+            if (has_truth) {  // (some owner in the ring is allowed: at most M steps)
+                uint32_t j = pos;
+                for (uint32_t s = 0; s < M; s++) {
+                    const uint32_t o = rv.own[j];
+                    if (tr[o]) {
+                        tk = o;
+                        break;
+                    }
+                    j = j + 1u == M ? 0u : j + 1u;
+                }
+            }
+            if (blockIdx.y == 0 && truth_owner) truth_owner[k] = tk;
+        }
+        for (uint32_t kk = 0; kk < cnt; kk++) {
+            const uint32_t i = __shfl(pos, (int)kk), t = __shfl(tk, (int)kk), first = __shfl(o0, (int)kk);
+            unsigned long long rem = walked & anyw, wr = 0, lo = 0;
+            if (t != NIL) wr = walked & ~anyw;  // views that allow nobody answer null
+            uint32_t* orow = OWN ? owners + (base + kk) * (uint64_t)V + (uint64_t)w * 64u : nullptr;
+            auto apply = [&](uint32_t o, unsigned long long p) {
+                unsigned long long hit = rem & p;
+                if (hit) {
+                    rem &= ~hit;
+                    if (o != t) {
+                        wr |= hit;
+                        if (!tr[o]) lo |= hit;
+                    }
+                    if constexpr (OWN) {
+                        while (hit) {
+                            orow[__builtin_ctzll(hit)] = o;
+                            hit &= hit - 1ull;
+                        }
+                    }
+                }
+            };
+            if (rem) apply(first, plane[(uint64_t)first * PW + w]);
+            uint32_t j = i + 1u == M ? 0u : i + 1u;
+            for (uint32_t steps = 1; steps < M && __ballot(rem != 0); steps += 4u) {
+                uint32_t o4[4];
+                unsigned long long p4[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    o4[q] = rv.own[j];
+                    j = j + 1u == M ? 0u : j + 1u;
+                }
+                if (rem) {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) p4[q] = plane[(uint64_t)o4[q] * PW + w];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) apply(o4[q], p4[q]);  // (steps past M revisit answered owners)
+                }
+            }
+            if (t != NIL) wr |= rem;  // (no allowed owner after M steps: null)
+            wr &= actw;
+            lo &= actw;
+            if (wr) {
+                if (key_wrong) atomicAdd(key_wrong + base + kk, (uint32_t)__popcll(wr));
+                while (wr) {
+                    atomicAdd(&s_wrong[lane * 64u + (uint32_t)__builtin_ctzll(wr)], 1u);
+                    wr &= wr - 1ull;
+                }
+                while (lo) {
+                    atomicAdd(&s_lost[lane * 64u + (uint32_t)__builtin_ctzll(lo)], 1u);
+                    lo &= lo - 1ull;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < nw * 64u; i += kRouteThreads) {
+        const uint64_t v = (uint64_t)w0 * 64u + i;
+        if (v >= V) break;
+        const uint32_t a = s_wrong[i], b = s_lost[i];
+        if (a && wrong) atomicAdd(wrong + v, (unsigned long long)a);
+        if (b && lost) atomicAdd(lost + v, (unsigned long long)b);
+    }
+}
+
+// Outputs as rp_ring_route_views_dev documents; everything is queued on st.
+static void route_views(Ring& r, const uint8_t* keys, const uint64_t* off, uint32_t stride, const uint32_t* hashes,
+                        uint64_t n, const uint8_t* rows, uint64_t row_stride, uint8_t bit, uint32_t V,
+                        const uint32_t* col, uint32_t id_cap, const uint8_t* truth, const uint8_t* active,
+                        int accumulate, uint64_t* wrong, uint64_t* lost, uint32_t* key_wrong, uint32_t* truth_owner,
+                        uint32_t* owners, hipStream_t st) {
+    const uint32_t idb = r.nt.size();
+    RP_REQUIRE(id_cap >= idb, "route_views: id_cap is below the ring's id bound (rp_ring_id_bound)");
+    RP_REQUIRE(n == 0 || ((keys != nullptr) != (hashes != nullptr)),
+               "route_views: exactly one of the key buffer and the hash buffer");
+    RP_REQUIRE(n == 0 || hashes || stride || off, "route_views: null key offsets");
+    RP_REQUIRE(V == 0 || rows, "route_views: null view rows");
+    RP_REQUIRE(bit != 0, "route_views: bit is zero");
+    RP_REQUIRE(V == 0 || col || row_stride >= id_cap, "route_views: without a column map row_stride covers id_cap");
+    const uint32_t PW = V ? (V + 63u) / 64u : 1u;
+    RP_REQUIRE(PW <= 65535u, "route_views: at most 4,194,240 views a call");
+    // the ring is rebuilt on r.st; make the caller's stream wait for it
+    if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
+    if (!accumulate && V) {
+        if (wrong) RP_HIP(hipMemsetAsync(wrong, 0, (uint64_t)V * 8, st));
+        if (lost) RP_HIP(hipMemsetAsync(lost, 0, (uint64_t)V * 8, st));
+    }
+    if (n == 0) return;
+    if (key_wrong) RP_HIP(hipMemsetAsync(key_wrong, 0, n * 4, st));
+    if (owners && V) RP_HIP(hipMemsetAsync(owners, 0xFF, n * V * 4, st));  // RP_NULL_ID until a view answers
+    if (r.M == 0) {  // every owner is null, the truth's too
+        if (truth_owner) RP_HIP(hipMemsetAsync(truth_owner, 0xFF, n * 4, st));
+        return;
+    }
+    RouteScratch& ws = r.route_ws;
+    ws.use_on(st);
+    ws.plane.reserve((uint64_t)idb * PW);
+    ws.meta.reserve(2ull * PW + 1);
+    ws.tr.reserve(idb);
+    unsigned long long* any = ws.meta.p;
+    unsigned long long* act = any + PW;
+    unsigned long long* tany = act + PW;
+    RP_HIP(hipMemsetAsync(ws.meta.p, 0, (2ull * PW + 1) * 8, st));
+    hipLaunchKernelGGL(k_route_pack, dim3((idb + kRoutePackThreads - 1) / kRoutePackThreads, PW),
+                       dim3(kRoutePackThreads), 0, st, rows, row_stride, bit, V, col, idb, r.d_inring.p, r.inring_n,
+                       truth, active, PW, ws.plane.p, any, act, tany, ws.tr.p);
+    RP_HIP(hipGetLastError());
+    uint64_t vblock = std::min<uint64_t>(env_pos("RP_ROUTE_VBLOCK", kRouteVBlock), kRouteVBlock);
+    vblock = std::max<uint64_t>(64, vblock & ~63ull);
+    const uint32_t VBW = (uint32_t)(vblock / 64), nvb = (PW + VBW - 1) / VBW;
+    const size_t lds = (size_t)std::min(VBW, PW) * 128u * sizeof(uint32_t);
+    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
+    const RingView rv = r.view();
+    const uint64_t gcap = (uint64_t)load_cus(r.device) * 4;  // 512 threads at <= 64 VGPRs: four workgroups a CU
+    for (uint64_t k0 = 0; k0 < n; k0 += kRouteChunk) {
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(kRouteChunk, n - k0);
+        const unsigned g = (unsigned)std::max<uint64_t>(
+            1, std::min<uint64_t>(gcap, ((uint64_t)cnt + kRouteThreads - 1) / kRouteThreads));
+#define RP_ROUTE(FIXED, OWN)                                                                                        \
+    hipLaunchKernelGGL((k_route<FIXED, OWN>), dim3(g, nvb), dim3(kRouteThreads), lds, st,                          \
+                       hashes ? nullptr : (stride ? keys + k0 * stride : keys),                                    \
+                       (!hashes && !stride) ? off + k0 : nullptr, stride, hashes ? hashes + k0 : nullptr, cnt, rv, \
+                       ws.plane.p, any, act, tany, ws.tr.p, PW, V, VBW,                                            \
+                       reinterpret_cast<unsigned long long*>(wrong), reinterpret_cast<unsigned long long*>(lost),  \
+                       key_wrong ? key_wrong + k0 : nullptr, truth_owner ? truth_owner + k0 : nullptr,             \
+                       owners ? owners + k0 * V : nullptr)
+        if (fixed36) {
+            if (owners) RP_ROUTE(true, true);
+            else RP_ROUTE(true, false);
+        } else {
+            if (owners) RP_ROUTE(false, true);
+            else RP_ROUTE(false, false);
+        }
+#undef RP_ROUTE
+        RP_HIP(hipGetLastError());
+    }
+}
+
 }  // namespace rp
 
 // ==================================================================================== C ABI
@@ -4273,6 +4560,10 @@ struct rp_ring_snap {
 
 using rp::guard;
 using rp::guard_host;
+
+namespace rp {
+int ring_device(const rp_ring* h) { return h ? h->impl.device : -1; }  // (rp_sim_routing's device check)
+}
 
 static rp::Ring& R(rp_ring* r) {
     if (!r) throw rp::Error(rp::RP_EINVAL, "null ring handle");
@@ -5122,6 +5413,96 @@ int rp_ring_handoff_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_
         RP_REQUIRE(n == 0 || hashes, "handoff_hashes: null hash buffer");
         host_handoff(r, s, nullptr, nullptr, 0, hashes, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot,
                      ndest, count);
+    });
+}
+
+// ---- routing agreement
+
+int rp_ring_route_views_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_off, uint32_t stride,
+                            const uint32_t* d_hashes, uint64_t n, const uint8_t* d_rows, uint64_t row_stride,
+                            uint8_t bit, uint32_t n_views, const uint32_t* d_col, uint32_t id_cap,
+                            const uint8_t* d_truth, const uint8_t* d_active, int accumulate, uint64_t* d_wrong,
+                            uint64_t* d_lost, uint32_t* d_key_wrong, uint32_t* d_truth_owner, uint32_t* d_owners,
+                            void* stream) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        svc_stop(r);
+        rp::route_views(r, d_keys, d_off, stride, d_hashes, n, d_rows, row_stride, bit, n_views, d_col, id_cap,
+                        d_truth, d_active, accumulate, d_wrong, d_lost, d_key_wrong, d_truth_owner, d_owners,
+                        rp::as_stream(stream));
+    });
+}
+
+int rp_ring_route_views(rp_ring* h, const char* keys, const uint64_t* off, uint32_t stride, const uint32_t* hashes,
+                        uint64_t n, const uint8_t* rows, uint64_t row_stride, uint8_t bit, uint32_t n_views,
+                        const uint32_t* col, uint32_t id_cap, const uint8_t* truth, const uint8_t* active,
+                        int accumulate, uint64_t* wrong, uint64_t* lost, uint32_t* key_wrong, uint32_t* truth_owner,
+                        uint32_t* owners) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const uint64_t V = n_views, idb = r.nt.size();
+        RP_REQUIRE(id_cap >= idb, "route_views: id_cap is below the ring's id bound (rp_ring_id_bound)");
+        RP_REQUIRE(n == 0 || ((keys != nullptr) != (hashes != nullptr)),
+                   "route_views: exactly one of the key buffer and the hash buffer");
+        RP_REQUIRE(n == 0 || hashes || stride || off, "route_views: null key offsets");
+        RP_REQUIRE(V == 0 || rows, "route_views: null view rows");
+        svc_stop(r);
+        const uint8_t* dk = nullptr;
+        const uint64_t* doff = nullptr;
+        const uint32_t* dh = nullptr;
+        if (n && hashes) {
+            r.io_a.reserve(n);
+            RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
+            dh = r.io_a.p;
+        } else if (n) {
+            const uint64_t bytes = stride ? n * stride : off[n];
+            r.io_keys.reserve(bytes + 16);
+            RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
+            dk = r.io_keys.p;
+            if (!stride) {
+                r.io_off.reserve(n + 1);
+                RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
+                doff = r.io_off.p;
+            }
+        }
+        rp::RouteScratch& ws = r.route_ws;
+        ws.use_on(r.st);
+        // io8 = [rows V * row_stride | truth row_stride | active V]
+        const uint64_t rb = V * row_stride;
+        ws.io8.reserve(rb + row_stride + V + 1);
+        uint8_t* drows = ws.io8.p;
+        uint8_t* dtruth = truth ? drows + rb : nullptr;
+        uint8_t* dact = active ? drows + rb + row_stride : nullptr;
+        if (rb) RP_HIP(hipMemcpyAsync(drows, rows, rb, hipMemcpyHostToDevice, r.st));
+        if (truth && row_stride) RP_HIP(hipMemcpyAsync(dtruth, truth, row_stride, hipMemcpyHostToDevice, r.st));
+        if (active && V) RP_HIP(hipMemcpyAsync(dact, active, V, hipMemcpyHostToDevice, r.st));
+        // io32 = [col idb | key_wrong n | truth_owner n | owners n * V], io64 = [wrong V | lost V]
+        ws.io32.reserve(idb + 2 * n + n * V + 1);
+        uint32_t* dcol = col ? ws.io32.p : nullptr;
+        uint32_t* dkw = key_wrong ? ws.io32.p + idb : nullptr;
+        uint32_t* dto = truth_owner ? ws.io32.p + idb + n : nullptr;
+        uint32_t* dow = owners ? ws.io32.p + idb + 2 * n : nullptr;
+        if (col && idb) RP_HIP(hipMemcpyAsync(dcol, col, idb * 4, hipMemcpyHostToDevice, r.st));
+        ws.io64.reserve(2 * V + 1);
+        unsigned long long* dwr = wrong ? ws.io64.p : nullptr;
+        unsigned long long* dlo = lost ? ws.io64.p + V : nullptr;
+        if (accumulate && V) {
+            if (wrong) RP_HIP(hipMemcpyAsync(dwr, wrong, V * 8, hipMemcpyHostToDevice, r.st));
+            if (lost) RP_HIP(hipMemcpyAsync(dlo, lost, V * 8, hipMemcpyHostToDevice, r.st));
+        }
+        rp::route_views(r, dk, doff, stride, dh, n, drows, row_stride, bit, n_views, dcol, id_cap, dtruth, dact,
+                        accumulate, reinterpret_cast<uint64_t*>(dwr), reinterpret_cast<uint64_t*>(dlo), dkw, dto, dow,
+                        r.st);
+        if (V) {
+            if (wrong) RP_HIP(hipMemcpyAsync(wrong, dwr, V * 8, hipMemcpyDeviceToHost, r.st));
+            if (lost) RP_HIP(hipMemcpyAsync(lost, dlo, V * 8, hipMemcpyDeviceToHost, r.st));
+        }
+        if (n) {
+            if (key_wrong) RP_HIP(hipMemcpyAsync(key_wrong, dkw, n * 4, hipMemcpyDeviceToHost, r.st));
+            if (truth_owner) RP_HIP(hipMemcpyAsync(truth_owner, dto, n * 4, hipMemcpyDeviceToHost, r.st));
+            if (owners && V) RP_HIP(hipMemcpyAsync(owners, dow, n * V * 4, hipMemcpyDeviceToHost, r.st));
+        }
+        RP_HIP(hipStreamSynchronize(r.st));
     });
 }
 

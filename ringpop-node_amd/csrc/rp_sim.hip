@@ -51,6 +51,10 @@
 #include "rp_swim.h"
 
 namespace rp {
+int ring_device(const rp_ring* h);  // rp_ring.hip: the device a ring handle lives on (-1: null)
+}
+
+namespace rp {
 
 namespace {
 
@@ -3292,6 +3296,15 @@ __global__ void k_conv_local(SimDev S, const uint8_t* __restrict__ skip, const u
     }
 }
 
+// rp_sim_routing's default truth on an unsharded handle: member a really serves when it is up and
+// its own status in its own view is not `leave` (truth bytes carry the IN_RING bit, as the rows do)
+__global__ void k_sim_truth(const uint8_t* __restrict__ st, const uint8_t* __restrict__ dead, uint32_t N,
+                            uint8_t* __restrict__ truth) {
+    const uint32_t a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= N) return;
+    truth[a] = (!dead[a] && (st[(uint64_t)a * N + a] & ST_MASK) != ST_LEAVE) ? IN_RING : 0;
+}
+
 __global__ void k_sim_init(SimDev S) {
     const uint64_t NN = (uint64_t)S.NL * S.N;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < NN; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -3447,6 +3460,13 @@ struct Sim {
     uint64_t sent_msgs = 0, sent_recs = 0, base_len = 0;  // traffic counters (rp_sim_counters)
     int64_t round = 0;
     int next_stage = 0;  // 0..4 within a round
+    // rp_sim_routing: the column map ring id -> member (cached per ring handle and id bound: a
+    // ring's interned ids never change), the truth bytes, and the host form's keys and outputs
+    const void* rt_ring = nullptr;
+    uint32_t rt_bound = 0;
+    DevBuf<uint32_t> rt_col, rt_u32;
+    DevBuf<uint8_t> rt_truth, rt_keys;
+    DevBuf<uint64_t> rt_off, rt_u64;
 
     uint32_t cus = 0;  // compute units of the device (first refresh)
     void refresh_checksums() {
@@ -4525,6 +4545,112 @@ int rp_sim_view(rp_sim* s, uint32_t v, uint8_t* status, int64_t* inc) {
         RP_HIP(hipStreamSynchronize(S.st));
         if (status)
             for (uint32_t a = 0; a < S.N; a++) status[a] &= rp::ST_MASK;
+    });
+}
+
+int rp_sim_ring_members(rp_sim* s, uint32_t v, uint8_t* in_ring) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        RP_REQUIRE(v >= S.v0 && v < S.v0 + S.NL, "sim_ring_members: node not in this shard");
+        RP_REQUIRE(in_ring, "sim_ring_members: null output");
+        RP_HIP(hipMemcpyAsync(in_ring, S.st_.p + (uint64_t)(v - S.v0) * S.N, S.N, hipMemcpyDeviceToHost, S.st));
+        RP_HIP(hipStreamSynchronize(S.st));
+        for (uint32_t a = 0; a < S.N; a++) in_ring[a] = (in_ring[a] & rp::IN_RING) ? 1 : 0;
+    });
+}
+
+// Every local node's ring membership as views of `ring`, on the handle's stream: only
+// rp_ring_route_views_dev over the status rows (bit IN_RING), after the queued rounds.
+static void sim_routing(rp::Sim& S, rp_ring* ring, const char* keys, const uint64_t* off, uint32_t stride,
+                        const uint32_t* hashes, uint64_t n, const uint8_t* truth, uint64_t* wrong, uint64_t* lost,
+                        uint32_t* key_wrong, uint32_t* truth_owner) {
+    RP_REQUIRE(ring, "sim_routing: null ring handle");
+    RP_REQUIRE(rp::ring_device(ring) == S.device, "sim_routing: the ring lives on another device than the simulator");
+    RP_REQUIRE(S.G == 1 || truth, "sim_routing: a sharded handle needs the truth (no shard holds every node's own status)");
+    RP_REQUIRE(S.G == 1 || S.next_stage == 0, "sim_routing: a sharded handle routes at a round boundary (before stage 0)");
+    RP_REQUIRE(n == 0 || hashes || (keys && (stride || off)), "sim_routing: null key buffer");
+    auto ring_call = [](int rc) {
+        if (rc) throw rp::Error(rc, rp::last_error());
+    };
+    uint32_t idb = 0;
+    ring_call(rp_ring_id_bound(ring, &idb));
+    RP_HIP(hipSetDevice(S.device));
+    const uint32_t N = S.N, NL = S.NL;
+    if (S.rt_ring != ring || S.rt_bound != idb || !S.rt_col.p) {
+        std::vector<uint32_t> col(std::max<uint32_t>(idb, 1), RP_NULL_ID);
+        for (uint32_t a = 0; a < N; a++) {
+            uint32_t id = RP_NULL_ID;
+            const uint64_t b = S.nt.h_noff[a], e = S.nt.h_noff[a + 1];
+            ring_call(rp_ring_server_id(ring, reinterpret_cast<const char*>(S.nt.h_bytes.data()) + b, (uint32_t)(e - b), &id));
+            if (id < idb) col[id] = a;
+        }
+        S.rt_ring = nullptr;
+        S.rt_col.reserve(col.size());
+        RP_HIP(hipMemcpyAsync(S.rt_col.p, col.data(), col.size() * 4, hipMemcpyHostToDevice, S.st));
+        RP_HIP(hipStreamSynchronize(S.st));  // (col is reused by nobody after this scope)
+        S.rt_ring = ring;
+        S.rt_bound = idb;
+    }
+    std::vector<uint8_t> tb;
+    S.rt_truth.reserve(N);
+    if (truth) {
+        tb.resize(N);
+        for (uint32_t a = 0; a < N; a++) tb[a] = truth[a] ? rp::IN_RING : 0;
+        RP_HIP(hipMemcpyAsync(S.rt_truth.p, tb.data(), N, hipMemcpyHostToDevice, S.st));
+    } else {
+        hipLaunchKernelGGL(rp::k_sim_truth, dim3(rp::grid_for(N, 256, 1u << 24)), dim3(256), 0, S.st, S.st_.p,
+                           S.dead.p, N, S.rt_truth.p);
+        RP_HIP(hipGetLastError());
+    }
+    const uint8_t* dk = nullptr;
+    const uint64_t* doff = nullptr;
+    const uint32_t* dh = nullptr;
+    S.rt_u32.reserve(3 * n + 1);
+    if (n && hashes) {
+        RP_HIP(hipMemcpyAsync(S.rt_u32.p + 2 * n, hashes, n * 4, hipMemcpyHostToDevice, S.st));
+        dh = S.rt_u32.p + 2 * n;
+    } else if (n) {
+        const uint64_t bytes = stride ? n * stride : off[n];
+        S.rt_keys.reserve(bytes + 16);
+        RP_HIP(hipMemcpyAsync(S.rt_keys.p, keys, bytes, hipMemcpyHostToDevice, S.st));
+        dk = S.rt_keys.p;
+        if (!stride) {
+            S.rt_off.reserve(n + 1);
+            RP_HIP(hipMemcpyAsync(S.rt_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, S.st));
+            doff = S.rt_off.p;
+        }
+    }
+    S.rt_u64.reserve(2ull * NL + 1);
+    uint64_t* dwr = wrong ? S.rt_u64.p : nullptr;
+    uint64_t* dlo = lost ? S.rt_u64.p + NL : nullptr;
+    uint32_t* dkw = key_wrong ? S.rt_u32.p : nullptr;
+    uint32_t* dto = truth_owner ? S.rt_u32.p + n : nullptr;
+    ring_call(rp_ring_route_views_dev(ring, dk, doff, stride, dh, n, S.st_.p, N, rp::IN_RING, NL, S.rt_col.p, idb,
+                                      S.rt_truth.p, S.rt_truth.p + S.v0, 0, dwr, dlo, dkw, dto, nullptr, S.st));
+    RP_HIP(hipSetDevice(S.device));
+    if (NL) {
+        if (wrong) RP_HIP(hipMemcpyAsync(wrong, dwr, 8ull * NL, hipMemcpyDeviceToHost, S.st));
+        if (lost) RP_HIP(hipMemcpyAsync(lost, dlo, 8ull * NL, hipMemcpyDeviceToHost, S.st));
+    }
+    if (n) {
+        if (key_wrong) RP_HIP(hipMemcpyAsync(key_wrong, dkw, n * 4, hipMemcpyDeviceToHost, S.st));
+        if (truth_owner) RP_HIP(hipMemcpyAsync(truth_owner, dto, n * 4, hipMemcpyDeviceToHost, S.st));
+    }
+    RP_HIP(hipStreamSynchronize(S.st));
+}
+
+int rp_sim_routing(rp_sim* s, rp_ring* ring, const char* keys, const uint64_t* off, uint32_t stride, uint64_t n,
+                   const uint8_t* truth, uint64_t* wrong, uint64_t* lost, uint32_t* key_wrong, uint32_t* truth_owner) {
+    return guard([&] {
+        sim_routing(SM(s), ring, keys, off, stride, nullptr, n, truth, wrong, lost, key_wrong, truth_owner);
+    });
+}
+
+int rp_sim_routing_hashes(rp_sim* s, rp_ring* ring, const uint32_t* hashes, uint64_t n, const uint8_t* truth,
+                          uint64_t* wrong, uint64_t* lost, uint32_t* key_wrong, uint32_t* truth_owner) {
+    return guard([&] {
+        RP_REQUIRE(n == 0 || hashes, "sim_routing_hashes: null hash buffer");
+        sim_routing(SM(s), ring, nullptr, nullptr, 0, hashes, n, truth, wrong, lost, key_wrong, truth_owner);
     });
 }
 

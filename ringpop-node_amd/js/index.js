@@ -297,6 +297,27 @@ HashRing.prototype.handoffNames = function handoffNames(keys, plan) {
     return out;
 };
 
+// Routing agreement: routeViews(keys, views, truth) answers every key's owner under many views of
+// this ring in one device call. views: arrays of server names (the servers each view's ring
+// holds); truth: one more such array (omitted: every server of this ring). Returns {owners: per
+// key the owner name under every view (null: none), truth: per key the owner name under the truth,
+// wrong / lost: per view how many keys go to another server than the truth's / to a server the
+// truth does not hold}. Names this ring does not hold are ignored.
+HashRing.prototype.routeViews = function routeViews(keys, views, truth) {
+    var r = native.ringRouteViews(this._h, this._customHash ? this._hashes(keys) : keys, views,
+        truth === undefined ? null : truth);
+    var self = this, V = r.views, owners = new Array(keys.length), t = new Array(keys.length);
+    function nm(id) { return id === 0xFFFFFFFF ? null : self.ownerName(id); }
+    for (var k = 0; k < keys.length; k++) {
+        var row = new Array(V);
+        for (var v = 0; v < V; v++) { row[v] = nm(r.owners[k * V + v]); }
+        owners[k] = row;
+        t[k] = nm(r.truthOwner[k]);
+    }
+    return {owners: owners, truth: t, wrong: Array.prototype.slice.call(r.wrong),
+        lost: Array.prototype.slice.call(r.lost)};
+};
+
 // Range hand-off, and planning a change before any key exists: movedRanges(snap, n) gives the hash
 // intervals [lo, hi] (inclusive, ascending, maximal runs of one pair of rows) on which lookupN(h, n)
 // differs between the snapshot and the ring now, in one device pass over the two token sets and

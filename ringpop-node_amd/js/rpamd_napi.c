@@ -720,6 +720,124 @@ static napi_value js_ring_handoff(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* One row of rp_ring_route_views' byte matrix from a JS array of server names: row[id] = 1 for the
+ * names the ring has interned (others are ignored). 0, or -1 with a pending JS exception. */
+static int route_row(napi_env env, rp_ring *r, napi_value names, uint8_t *row, uint32_t bound) {
+    strpack_t s;
+    if (strpack_from_array(env, names, &s)) return -1;
+    memset(row, 0, bound ? bound : 1);
+    int rc = 0;
+    for (uint32_t i = 0; i < s.n && !rc; i++) {
+        uint32_t id = RP_NULL_ID;
+        rc = rp_ring_server_id(r, s.bytes + s.off64[i], (uint32_t)(s.off64[i + 1] - s.off64[i]), &id);
+        if (!rc && id < bound) row[id] = 1;
+    }
+    strpack_free(&s);
+    if (rc) {
+        napi_throw_error(env, "ERR_RINGPOP_AMD", rp_last_error());
+        return -1;
+    }
+    return 0;
+}
+
+/* ringRouteViews(h, keys[] | Uint32Array hashes, views: [[server names]], truth: [names] | null) ->
+ * {views, wrong, lost: Float64Array[views], keyWrong, truthOwner: Uint32Array[keys],
+ * owners: Uint32Array[keys * views]}: every key's owner under every view of this ring at once
+ * (rp_ring_route_views; 0xFFFFFFFF = none). Counts are Numbers: exact below 2^53. */
+static napi_value js_ring_route_views(napi_env env, napi_callback_info info) {
+    ARGS(4);
+    handle_t *h = get_handle(env, argv[0], 1);
+    if (!h) return NULL;
+    rp_ring *r = (rp_ring *)h->p;
+    uint32_t bound = 0;
+    RP_OK(rp_ring_id_bound(r, &bound));
+    bool isarr = false;
+    napi_is_array(env, argv[2], &isarr);
+    if (!isarr) {
+        napi_throw_type_error(env, NULL, "views must be an array of arrays of server names");
+        return NULL;
+    }
+    uint32_t nv = 0;
+    napi_get_array_length(env, argv[2], &nv);
+    const size_t rs = bound ? bound : 1;
+    uint8_t *rows = (uint8_t *)calloc((size_t)(nv ? nv : 1) * rs, 1), *truth = NULL;
+    for (uint32_t v = 0; v < nv; v++) {
+        napi_value e;
+        napi_get_element(env, argv[2], v, &e);
+        if (route_row(env, r, e, rows + (size_t)v * rs, bound)) {
+            free(rows);
+            return NULL;
+        }
+    }
+    if (!is_nullish(env, argv[3])) {
+        truth = (uint8_t *)calloc(rs, 1);
+        if (route_row(env, r, argv[3], truth, bound)) {
+            free(rows);
+            free(truth);
+            return NULL;
+        }
+    }
+    bool is_typed = false;
+    napi_is_typedarray(env, argv[1], &is_typed);
+    size_t n = 0;
+    void *hv = NULL;
+    strpack_t keys;
+    memset(&keys, 0, sizeof(keys));
+    if (is_typed) {
+        if (typed_get(env, argv[1], napi_uint32_array, &hv, &n)) {
+            free(rows);
+            free(truth);
+            napi_throw_type_error(env, NULL, "hashes must be a Uint32Array");
+            return NULL;
+        }
+    } else {
+        if (strpack_from_array(env, argv[1], &keys)) {
+            free(rows);
+            free(truth);
+            return NULL;
+        }
+        n = keys.n;
+    }
+    const size_t nn = n ? n : 1, vv = nv ? nv : 1;
+    uint64_t *wrong = (uint64_t *)calloc(2 * vv, 8), *lost = wrong + vv;
+    uint32_t *kw = (uint32_t *)calloc(2 * nn + nn * vv, 4), *to = kw + nn, *ow = to + nn;
+    int rc = rp_ring_route_views(r, is_typed ? NULL : keys.bytes, is_typed ? NULL : keys.off64, 0,
+                                 is_typed ? (const uint32_t *)hv : NULL, n, rows, rs, 1, nv, NULL, bound, truth, NULL,
+                                 0, wrong, lost, kw, to, ow);
+    if (!is_typed) strpack_free(&keys);
+    napi_value out = NULL;
+    if (!rc) {
+        void *dw = NULL, *dl = NULL, *dk = NULL, *dt = NULL, *dow = NULL;
+        napi_value vw = new_typed(env, napi_float64_array, nv, 8, &dw);
+        napi_value vl = new_typed(env, napi_float64_array, nv, 8, &dl);
+        napi_value vk = new_typed(env, napi_uint32_array, n, 4, &dk);
+        napi_value vt = new_typed(env, napi_uint32_array, n, 4, &dt);
+        napi_value vo = new_typed(env, napi_uint32_array, n * nv, 4, &dow);
+        for (uint32_t v = 0; v < nv; v++) {
+            ((double *)dw)[v] = (double)wrong[v];
+            ((double *)dl)[v] = (double)lost[v];
+        }
+        if (n) {
+            memcpy(dk, kw, 4 * n);
+            memcpy(dt, to, 4 * n);
+            if (nv) memcpy(dow, ow, 4 * n * nv);
+        }
+        napi_create_object(env, &out);
+        napi_set_named_property(env, out, "views", make_u32(env, nv));
+        napi_set_named_property(env, out, "wrong", vw);
+        napi_set_named_property(env, out, "lost", vl);
+        napi_set_named_property(env, out, "keyWrong", vk);
+        napi_set_named_property(env, out, "truthOwner", vt);
+        napi_set_named_property(env, out, "owners", vo);
+    }
+    free(rows);
+    free(truth);
+    free(wrong);
+    free(kw);
+    RP_OK(rc);
+    return out;
+}
+
 /* The servers now in the ring (rp_ring_servers order) as {names: [..], counts: Float64Array}:
  * counts[i * w + q] = table[ids[i] * w + q]. Counts are Numbers: exact below 2^53. */
 static napi_value ring_named_counts(napi_env env, rp_ring *r, const uint64_t *table, size_t w) {
@@ -1632,6 +1750,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringSnapInfo", NULL, js_ring_snap_info, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedKeys", NULL, js_ring_moved_keys, NULL, NULL, NULL, napi_default, NULL},
         {"ringHandoff", NULL, js_ring_handoff, NULL, NULL, NULL, napi_default, NULL},
+        {"ringRouteViews", NULL, js_ring_route_views, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerLoad", NULL, js_ring_owner_load, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerShare", NULL, js_ring_owner_share, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedRanges", NULL, js_ring_moved_ranges, NULL, NULL, NULL, napi_default, NULL},
