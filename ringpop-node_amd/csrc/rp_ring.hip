@@ -768,6 +768,219 @@ __device__ unsigned long long g_lk_prof[10];
 #else
 #define RP_LKA(cv) 0u
 #endif
+constexpr uint32_t kLkAG = 64;  // second-window list slots per wave (8 % of 64 * KPL keys: ~41 at KPL 8)
+
+// The lean lookup's per-key stages, shared by k_lookupn_lean and k_lookupn_sorted: the index
+// record, window 1's start and load, the straight-line resolve with the per-wave second-window
+// list, and the listed keys' finish. KB: bits of a key's tile slot in a list word (2^KB >= the
+// tile's keys). A deferred key's tile slot goes to the caller's `defer`.
+template <int NEED, int KB>
+struct LkStages {
+    static constexpr uint32_t SPAN = 5 - NEED;  // last window-1 position that still holds NEED entries
+    const CompactView& cv;
+    const uint32_t omask, obit, bsh, rmask;
+    const __amdgpu_buffer_rsrc_t ent_r;
+    // lookupN(3) reads the hinted index when the ring has one (round 5; RP_LOOKUP_HINT=0: A/B)
+    const bool hinted;
+    const __amdgpu_buffer_rsrc_t idx_r;
+
+    __device__ __forceinline__ explicit LkStages(const CompactView& v)
+        : cv(v), omask((1u << v.ob) - 1u), obit(1u << v.ob), bsh(32u - v.cb), rmask((1u << (32u - v.cb)) - 1u),
+          ent_r(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(v.ent), 0, (int)v.ent_bytes, 0x00020000)),
+          hinted(NEED == 3 && v.idxh != nullptr && !(RP_LKA(v) & 4u)),
+          idx_r(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(hinted ? v.idxh : v.idx), 0,
+                                                  (int)v.idx_bytes, 0x00020000)) {}
+
+    __device__ __forceinline__ u32x4 load16(uint32_t pos) const {
+        return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ent_r, (int)(3u * pos), 0, 0));
+    }
+    static __device__ __forceinline__ void ent5v(const u32x4 v, uint32_t (&e)[5]) {
+        e[0] = v.x & 0xFFFFFFu;
+        e[1] = (v.x >> 24) | ((v.y & 0xFFFFu) << 8);
+        e[2] = (v.y >> 16) | ((v.z & 0xFFu) << 16);
+        e[3] = v.z >> 8;
+        e[4] = v.w & 0xFFFFFFu;
+    }
+    // Window 1's first entry within the bucket (round 3): the key's position in a bucket of bc
+    // tokens is about bc times its place in the bucket's hash range (r), so the window starts at
+    // max(0, floor(r bc) - 1). A window at w > 0 resolves positions w+1..w+2 (entry w below the key
+    // is the guard), one at 0 positions 0..2: 3.6 % of keys need a second window instead of 9.9 %
+    // (Poisson buckets of 1.9 tokens; lookupN(2): 3.3 % -> 1.6 %). Long buckets (> 10) keep w = 0,
+    // and so does lookup (NEED 1), whose window at 0 already resolves positions 0..4 (0.9 % of keys
+    // past it against 1.5 % with the predicted start).
+    // hint (the hinted index): the start moves by hint - 1 entries (1 = the plain prediction)
+    __device__ __forceinline__ uint32_t wstart(uint32_t hk, uint32_t bck, uint32_t hint) const {
+        const int fl = (int)((((hk << cv.cb) >> 24) * bck) >> 8) - 2 + (int)hint;
+        return (NEED >= 2 && cv.wpred && bck <= 10u && fl > 0) ? (uint32_t)fl : 0u;
+    }
+    // the index trip: the 8-B record of the key's group of 8 buckets
+    __device__ __forceinline__ u32x2 index_rec(uint32_t hk) const {
+        if (RP_LKA(cv) & 4u)  // diagnostics: no index trip (a record made from the hash)
+            return u32x2{(uint32_t)(((uint64_t)hk * (cv.M - 32u)) >> 32), hk & 0x11111111u};
+        return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(idx_r, (int)((hk >> (bsh + 3u)) * 8u), 0, 0));
+    }
+    // the window trip: the bucket start lo, its token count bc, window 1's start ws; returns the window
+    __device__ __forceinline__ u32x4 window(uint32_t hk, const u32x2 rec, uint32_t& lo, uint32_t& bc, uint32_t& ws) const {
+        const uint32_t s4 = ((hk >> bsh) & 7u) * 4u;
+        const uint32_t below = rec.y & ((1u << s4) - 1u);
+        uint32_t base = rec.x, hint = 1u;
+        if (hinted) {  // base = pred(g) + the 14-bit delta; the bucket's 2-bit hint
+            const uint32_t g = hk >> (bsh + 3u);
+            base = (uint32_t)(((uint64_t)g * cv.M) >> (cv.cb - 3u)) + (uint32_t)((int32_t)(rec.x << 18) >> 18);
+            hint = (rec.x >> (14u + (s4 >> 1))) & 3u;
+        }
+        lo = base + __builtin_amdgcn_sad_u8(below & 0x0F0F0F0Fu, 0u,
+                                            __builtin_amdgcn_sad_u8((below >> 4) & 0x0F0F0F0Fu, 0u, 0u));
+        bc = (rec.y >> s4) & 15u;
+        ws = wstart(hk, bc, hint);
+        if (RP_LKA(cv) & 26u) {  // diagnostics: 2 = windows rounded down to 16 B (no line crossing);
+                                // 8 = no window trip (entries made from the record); 16 = windows
+                                // rounded down to 4 B (dword-aligned, still crossing lines)
+            const uint32_t pos = lo + ws;
+            return (RP_LKA(cv) & 8u) ? u32x4{rec.x, rec.y, hk, pos}
+                                     : __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                                                    ent_r, (int)((3u * pos) & ((RP_LKA(cv) & 2u) ? ~15u : ~3u)), 0, 0));
+        }
+        return load16(lo + ws);
+    }
+    // Window 1 of the key at tile slot kk: its row goes to so (and its count to cnt, the tile's
+    // counts or null) when the window resolves it; else it joins the wave's list agw (nag: the
+    // wave-uniform list length), or is deferred. Every lane of the wave calls this together.
+    template <class Defer>
+    __device__ __forceinline__ void resolve(const u32x4 win, uint32_t hk, uint32_t lo, uint32_t bc, uint32_t w,
+                                            uint32_t kk, uint32_t& nag, uint32_t (*agw)[kLkAG], uint32_t* so,
+                                            uint8_t* cnt, Defer&& defer) const {
+        uint32_t e[5];
+        ent5v(win, e);
+        const uint32_t K = ((hk & rmask) >> cv.fsh) << cv.ob;
+        uint32_t lt = 0;  // in-bucket window entries below the key: the position is lo + w + lt
+        bool tie = false;
+#pragma unroll
+        for (int j = 0; j < 5; j++) {
+            const bool inb = (uint32_t)j + w < bc;
+            lt += (inb && e[j] < K);
+            tie |= (inb && e[j] - K < obit);
+        }
+        uint32_t r[NEED];
+#pragma unroll
+        for (int q = 0; q < NEED; q++) {
+            uint32_t v = e[q] & omask;
+#pragma unroll
+            for (uint32_t d = 1; d <= SPAN; d++) v = lt == d ? (e[q + d] & omask) : v;
+            r[q] = v;
+        }
+        bool dup = false;
+#pragma unroll
+        for (int a = 0; a < NEED; a++)
+#pragma unroll
+            for (int b = a + 1; b < NEED; b++) dup |= r[a] == r[b];
+        bool slow = (tie && !cv.exact) | (lo + 20u > cv.M);
+        const bool under = w > 0u && lt == 0u;  // the key lies before window 1's first entry
+        const bool again = !slow && (lt > SPAN || dup || under) && !(RP_LKA(cv) & 1u);  // 1: diagnostics
+        const uint64_t m = __ballot(again);
+        const uint32_t pos = nag + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        nag += (uint32_t)__popcll(m);
+        if (again) {
+            if (pos < kLkAG) {
+                // under: search from w - 2 (the position is at most w), guarded when > 0; past
+                // window 1 inside the bucket: search on from w + 5; else the position is known
+                const uint32_t b0 = under ? (w > 2u ? w - 2u : 0u) : w + 5u;
+                const bool search = under || (lt == 5u && bc > w + 5u);
+                agw[0][pos] = lo + (search ? b0 : w + lt);
+                agw[1][pos] = K;
+                agw[2][pos] = kk | (bc << KB) | ((uint32_t)search << (KB + 4)) | ((search ? b0 : 0u) << (KB + 5)) |
+                              ((uint32_t)(under && b0 > 0u) << (KB + 9));
+            } else {
+                slow = true;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < NEED; q++) so[kk * NEED + q] = r[q];
+            if (cnt) cnt[kk] = (uint8_t)NEED;
+        }
+        if (slow) defer(kk);
+    }
+    // a listed key's second window (held by one lane): finish it, write its row into `row`
+    template <class Defer>
+    __device__ __forceinline__ void finish2(const u32x4 win, uint32_t K, uint32_t w2, uint32_t* row, uint8_t* cnt,
+                                            Defer&& defer) const {
+        const uint32_t kk = w2 & ((1u << KB) - 1u), bck = (w2 >> KB) & 15u, b0 = (w2 >> (KB + 5)) & 15u;
+        uint32_t e2[5];
+        ent5v(win, e2);
+        uint32_t off = 0;
+        bool slow = false;
+        if ((w2 >> (KB + 4)) & 1u) {  // window 2 holds bucket entries b0..b0+4: search it
+            bool tie = false;
+#pragma unroll
+            for (int j = 0; j < 5; j++) {
+                const bool inb = (uint32_t)j + b0 < bck;
+                off += (inb && e2[j] < K);
+                tie |= (inb && e2[j] - K < obit);
+            }
+            // past this window too; or (guard) the key may lie before entry b0
+            slow = (tie && !cv.exact) | (off == 5u && bck > b0 + 5u) | (((w2 >> (KB + 9)) & 1u) && off == 0u);
+        }
+        uint32_t res[4] = {NIL, NIL, NIL, NIL};
+        const uint32_t rc = dedupe5(e2, off, omask, NEED, res);
+        slow |= rc < (uint32_t)NEED;
+        if (slow) defer(kk);
+#pragma unroll
+        for (int q = 0; q < NEED; q++) row[kk * NEED + q] = res[q];
+        if (cnt) cnt[kk] = (uint8_t)rc;
+    }
+};
+
+// The key stage (STG 0): every lane loads all its 16-B pieces of the tile of THREADS * KPL keys
+// into registers first (non-temporal), then the HS slices pass through the LDS stage sk one after
+// another and are hashed: h[k] is the hash of the key at tile slot tid + k * THREADS. `issued`
+// runs once the loads are issued, `arrived` once the first slice is in LDS.
+// WAVE: THREADS is 64 and the tile is one wave's own (sk: the wave's own LDS stage, tid: the
+// lane): the slices are exchanged between the wave's lanes only, with no workgroup barrier.
+template <int THREADS, int KPL, int HS, bool WAVE = false, class Issued, class Arrived>
+__device__ __forceinline__ void lk_key_stage(const uint8_t* __restrict__ tile_keys, uint32_t* sk, int tid,
+                                             uint32_t (&h)[KPL], Issued&& issued, Arrived&& arrived) {
+    constexpr int LEN = 36, W4 = LEN / 4;
+    constexpr int V4 = THREADS * KPL * W4 / 4;
+    constexpr int PER = (V4 + THREADS - 1) / THREADS;
+    constexpr int VS = V4 / HS;  // 16-B vectors per slice
+    static_assert(KPL % HS == 0 && V4 % HS == 0, "slices of whole keys");
+    const u32x4* s4 = reinterpret_cast<const u32x4*>(tile_keys);
+    u32x4 pre[PER];
+#pragma unroll
+    for (int q = 0; q < PER; q++) {
+        const int k = tid + q * THREADS;
+        if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
+    }
+    static_assert(!WAVE || THREADS == 64, "a wave's own tile");
+    auto meet = [] {
+        if constexpr (WAVE) {
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            __syncthreads();
+        }
+    };
+    issued();
+#pragma unroll
+    for (int hs = 0; hs < HS; hs++) {
+        if (hs) meet();  // the previous slice is hashed
+#pragma unroll
+        for (int q = 0; q < PER; q++) {
+            const int k = tid + q * THREADS;
+            if (k >= hs * VS && k < (hs + 1) * VS) reinterpret_cast<u32x4*>(sk)[k - hs * VS] = pre[q];
+        }
+        meet();
+        if (hs == 0) arrived();
+#pragma unroll
+        for (int k = hs * (KPL / HS); k < (hs + 1) * (KPL / HS); k++) {
+            uint32_t w[W4];
+#pragma unroll
+            for (int j = 0; j < W4; j++) w[j] = sk[(tid + (k - hs * (KPL / HS)) * THREADS) * W4 + j];
+            h[k] = fh::hash32_words<LEN>(w);
+        }
+    }
+}
+
 template <int KPL, int NEED, int HS = 1, bool FUSE = false, int STG = 0, int LH = 1>
 __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4))) void k_lookupn_lean(const uint8_t* __restrict__ keys, uint64_t ntiles,
                                                              CompactView cv, uint32_t* __restrict__ out,
@@ -778,83 +991,21 @@ __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4)))
     constexpr int LEN = 36, W4 = LEN / 4;
     constexpr int TK = kLkThreads * KPL;
     constexpr int V4 = TK * W4 / 4;
-    constexpr int PER = (V4 + kLkThreads - 1) / kLkThreads;
     constexpr int NW = kLkThreads / 64;
-    constexpr uint32_t SPAN = 5 - NEED;  // last window-1 position that still holds NEED entries
     static_assert((TK * W4) % 4 == 0 && (TK * NEED) % 4 == 0 && NEED >= 1 && NEED <= 4, "tile shape");
     static_assert(KPL % HS == 0 && V4 % HS == 0, "slices of whole keys");
     constexpr int SK = TK * W4 / HS, SO = TK * NEED;
-    constexpr int VS = V4 / HS;  // 16-B vectors per slice
     constexpr int SKR = STG ? 2 * SK : SK;  // STG 1 / 2: two slice buffers
     static_assert(STG == 0 || (SK * 4) % 1024 == 0, "DMA slices of whole 1-KB wave pieces");
     __shared__ __attribute__((aligned(16))) uint32_t lds[SKR > SO ? SKR : SO];
-    constexpr uint32_t AG = 64;  // list slots per wave (8 % of 64 * KPL keys: ~41 at KPL 8)
+    constexpr uint32_t AG = kLkAG;
     __shared__ uint32_t ag[NW][3][AG];  // per-wave second-window list: start, K, kk | bc << 12 | search << 16
     __shared__ uint32_t nslow_tile;
     uint32_t* const sk = lds;
     uint32_t* const so = lds;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t omask = (1u << cv.ob) - 1u, obit = 1u << cv.ob;
-    const uint32_t bsh = 32u - cv.cb;
-    const uint32_t rmask = (1u << bsh) - 1u;
-    const __amdgpu_buffer_rsrc_t ent_r =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(cv.ent), 0, (int)cv.ent_bytes, 0x00020000);
-    // lookupN(3) reads the hinted index when the ring has one (round 5; RP_LOOKUP_HINT=0: A/B)
-    const bool hinted = NEED == 3 && cv.idxh != nullptr && !(RP_LKA(cv) & 4u);
-    const __amdgpu_buffer_rsrc_t idx_r = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t*>(hinted ? cv.idxh : cv.idx), 0, (int)cv.idx_bytes, 0x00020000);
-    auto load16 = [&](uint32_t pos) {
-        return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(ent_r, (int)(3u * pos), 0, 0));
-    };
-    auto ent5v = [&](const u32x4 v, uint32_t (&e)[5]) {
-        e[0] = v.x & 0xFFFFFFu;
-        e[1] = (v.x >> 24) | ((v.y & 0xFFFFu) << 8);
-        e[2] = (v.y >> 16) | ((v.z & 0xFFu) << 16);
-        e[3] = v.z >> 8;
-        e[4] = v.w & 0xFFFFFFu;
-    };
-    // Window 1's first entry within the bucket (round 3): the key's position in a bucket of bc
-    // tokens is about bc times its place in the bucket's hash range (r), so the window starts at
-    // max(0, floor(r bc) - 1). A window at w > 0 resolves positions w+1..w+2 (entry w below the key
-    // is the guard), one at 0 positions 0..2: 3.6 % of keys need a second window instead of 9.9 %
-    // (Poisson buckets of 1.9 tokens; lookupN(2): 3.3 % -> 1.6 %). Long buckets (> 10) keep w = 0,
-    // and so does lookup (NEED 1), whose window at 0 already resolves positions 0..4 (0.9 % of keys
-    // past it against 1.5 % with the predicted start).
-    // hint (the hinted index): the start moves by hint - 1 entries (1 = the plain prediction)
-    auto wstart = [&](uint32_t hk, uint32_t bck, uint32_t hint) -> uint32_t {
-        const int fl = (int)((((hk << cv.cb) >> 24) * bck) >> 8) - 2 + (int)hint;
-        return (NEED >= 2 && cv.wpred && bck <= 10u && fl > 0) ? (uint32_t)fl : 0u;
-    };
-    // a listed key's second window (held by one lane): finish it, write its row into `row`
-    auto finish2 = [&](const u32x4 win, uint32_t K, uint32_t w2, uint32_t* row, uint8_t* cnt, uint32_t* nsl,
-                       uint32_t* slist) {
-        const uint32_t kk = w2 & 0xFFFu, bck = (w2 >> 12) & 15u, b0 = (w2 >> 17) & 15u;
-        uint32_t e2[5];
-        ent5v(win, e2);
-        uint32_t off = 0;
-        bool slow = false;
-        if ((w2 >> 16) & 1u) {  // window 2 holds bucket entries b0..b0+4: search it
-            bool tie = false;
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                const bool inb = (uint32_t)j + b0 < bck;
-                off += (inb && e2[j] < K);
-                tie |= (inb && e2[j] - K < obit);
-            }
-            // past this window too; or (guard) the key may lie before entry b0
-            slow = (tie && !cv.exact) | (off == 5u && bck > b0 + 5u) | (((w2 >> 21) & 1u) && off == 0u);
-        }
-        uint32_t res[4] = {NIL, NIL, NIL, NIL};
-        const uint32_t rc = dedupe5(e2, off, omask, NEED, res);
-        slow |= rc < (uint32_t)NEED;
-        if (slow) {
-            const uint32_t sp = atomicAdd(nsl, 1u);
-            if (sp < kSlowPerTile) slist[sp] = kk;
-        }
-#pragma unroll
-        for (int q = 0; q < NEED; q++) row[kk * NEED + q] = res[q];
-        if (cnt) cnt[kk] = (uint8_t)rc;
-    };
+    const LkStages<NEED, 12> lk(cv);
+    static_assert(TK <= (1 << 12), "a tile slot is 12 bits of a list word");
 #ifdef RP_LK_PROF
     uint64_t pa[6] = {0, 0, 0, 0, 0, 0}, ntl = 0;
 #endif
@@ -932,41 +1083,23 @@ __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4)))
                 }
             }
         } else {
-            const u32x4* s4 = reinterpret_cast<const u32x4*>(keys + base * LEN);
-            u32x4 pre[PER];
-#pragma unroll
-            for (int q = 0; q < PER; q++) {
-                const int k = tid + q * kLkThreads;
-                if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
-            }
-            if (tid == 0) nslow_tile = 0;
-#pragma unroll
-            for (int hs = 0; hs < HS; hs++) {
-                if (hs) __syncthreads();  // the previous slice is hashed
-#pragma unroll
-                for (int q = 0; q < PER; q++) {
-                    const int k = tid + q * kLkThreads;
-                    if (k >= hs * VS && k < (hs + 1) * VS) reinterpret_cast<u32x4*>(sk)[k - hs * VS] = pre[q];
-                }
-                __syncthreads();
+            lk_key_stage<kLkThreads, KPL, HS>(
+                keys + base * LEN, sk, tid, h, [&] { if (tid == 0) nslow_tile = 0; },
+                [&] {
 #ifdef RP_LK_PROF
-                if (hs == 0) {
                     LK_T(tk, sk[tid]);
                     pa[0] += tk - t0;
-                }
 #endif
-#pragma unroll
-                for (int k = hs * (KPL / HS); k < (hs + 1) * (KPL / HS); k++) {
-                    uint32_t w[W4];
-#pragma unroll
-                    for (int j = 0; j < W4; j++) w[j] = sk[(tid + (k - hs * (KPL / HS)) * kLkThreads) * W4 + j];
-                    h[k] = fh::hash32_words<LEN>(w);
-                }
-            }
+                });
         }
         LK_T(t2, h[KPL - 1]);
         __syncthreads();  // sk is reused as so below
         uint32_t nag = 0;  // wave-uniform length of this wave's list
+        uint8_t* const cnt_tile = counts ? counts + base : nullptr;
+        auto defer = [&](uint32_t kk) {  // to the tile's list, for the exact fix path
+            const uint32_t sp = atomicAdd(&nslow_tile, 1u);
+            if (sp < kSlowPerTile) slow_list[t * kSlowPerTile + sp] = kk;
+        };
         // LH > 1: the index and window trips run for KPL / LH keys at a time (fewer live
         // registers in this phase; A/B: RP_LOOKUP_LH)
         constexpr int KH = KPL / LH;
@@ -979,41 +1112,11 @@ __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4)))
         if (hh) __builtin_amdgcn_sched_barrier(0);
         u32x2 rec[KH];
 #pragma unroll
-        for (int kq = 0; kq < KH; kq++) {
-            const int k = hh * KH + kq;
-            if (RP_LKA(cv) & 4u)  // diagnostics: no index trip (a record made from the hash)
-                rec[kq] = u32x2{(uint32_t)(((uint64_t)h[k] * (cv.M - 32u)) >> 32), h[k] & 0x11111111u};
-            else
-                rec[kq] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(idx_r, (int)((h[k] >> (bsh + 3u)) * 8u), 0, 0));
-        }
+        for (int kq = 0; kq < KH; kq++) rec[kq] = lk.index_rec(h[hh * KH + kq]);
         uint32_t lo[KH], bc[KH], ws[KH];
         u32x4 win[KH];
 #pragma unroll
-        for (int kq = 0; kq < KH; kq++) {
-            const int k = hh * KH + kq;
-            const uint32_t s4 = ((h[k] >> bsh) & 7u) * 4u;
-            const uint32_t below = rec[kq].y & ((1u << s4) - 1u);
-            uint32_t base = rec[kq].x, hint = 1u;
-            if (hinted) {  // base = pred(g) + the 14-bit delta; the bucket's 2-bit hint
-                const uint32_t g = h[k] >> (bsh + 3u);
-                base = (uint32_t)(((uint64_t)g * cv.M) >> (cv.cb - 3u)) + (uint32_t)((int32_t)(rec[kq].x << 18) >> 18);
-                hint = (rec[kq].x >> (14u + (s4 >> 1))) & 3u;
-            }
-            lo[kq] = base + __builtin_amdgcn_sad_u8(below & 0x0F0F0F0Fu, 0u,
-                                                    __builtin_amdgcn_sad_u8((below >> 4) & 0x0F0F0F0Fu, 0u, 0u));
-            bc[kq] = (rec[kq].y >> s4) & 15u;
-            ws[kq] = wstart(h[k], bc[kq], hint);
-            if (RP_LKA(cv) & 26u) {  // diagnostics: 2 = windows rounded down to 16 B (no line crossing);
-                                    // 8 = no window trip (entries made from the record); 16 = windows
-                                    // rounded down to 4 B (dword-aligned, still crossing lines)
-                const uint32_t pos = lo[kq] + ws[kq];
-                win[kq] = (RP_LKA(cv) & 8u) ? u32x4{rec[kq].x, rec[kq].y, h[k], pos}
-                                           : __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                          ent_r, (int)((3u * pos) & ((RP_LKA(cv) & 2u) ? ~15u : ~3u)), 0, 0));
-            } else {
-                win[kq] = load16(lo[kq] + ws[kq]);
-            }
-        }
+        for (int kq = 0; kq < KH; kq++) win[kq] = lk.window(h[hh * KH + kq], rec[kq], lo[kq], bc[kq], ws[kq]);
 #ifdef RP_LK_PROF
         if (hh == 0) {
             LK_T(t3h, lo[KH - 1]);
@@ -1023,68 +1126,15 @@ __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4)))
 #pragma unroll
         for (int kq = 0; kq < KH; kq++) {
             const int k = hh * KH + kq;
-            uint32_t e[5];
-            ent5v(win[kq], e);
-            const uint32_t K = ((h[k] & rmask) >> cv.fsh) << cv.ob;
-            const uint32_t w = ws[kq];
-            uint32_t lt = 0;  // in-bucket window entries below the key: the position is lo + w + lt
-            bool tie = false;
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                const bool inb = (uint32_t)j + w < bc[kq];
-                lt += (inb && e[j] < K);
-                tie |= (inb && e[j] - K < obit);
-            }
-            uint32_t r[NEED];
-#pragma unroll
-            for (int q = 0; q < NEED; q++) {
-                uint32_t v = e[q] & omask;
-#pragma unroll
-                for (uint32_t d = 1; d <= SPAN; d++) v = lt == d ? (e[q + d] & omask) : v;
-                r[q] = v;
-            }
-            bool dup = false;
-#pragma unroll
-            for (int a = 0; a < NEED; a++)
-#pragma unroll
-                for (int b = a + 1; b < NEED; b++) dup |= r[a] == r[b];
-            const uint32_t kk = tid + k * kLkThreads;
-            bool slow = (tie && !cv.exact) | (lo[kq] + 20u > cv.M);
-            const bool under = w > 0u && lt == 0u;  // the key lies before window 1's first entry
-            const bool again = !slow && (lt > SPAN || dup || under) && !(RP_LKA(cv) & 1u);  // 1: diagnostics
-            const uint64_t m = __ballot(again);
-            const uint32_t pos = nag + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            nag += (uint32_t)__popcll(m);
-            if (again) {
-                if (pos < AG) {
-                    // under: search from w - 2 (the position is at most w), guarded when > 0; past
-                    // window 1 inside the bucket: search on from w + 5; else the position is known
-                    const uint32_t b0 = under ? (w > 2u ? w - 2u : 0u) : w + 5u;
-                    const bool search = under || (lt == 5u && bc[kq] > w + 5u);
-                    ag[wv][0][pos] = lo[kq] + (search ? b0 : w + lt);
-                    ag[wv][1][pos] = K;
-                    ag[wv][2][pos] = kk | (bc[kq] << 12) | ((uint32_t)search << 16) | ((search ? b0 : 0u) << 17) |
-                                     ((uint32_t)(under && b0 > 0u) << 21);
-                } else {
-                    slow = true;
-                }
-            } else {
-#pragma unroll
-                for (int q = 0; q < NEED; q++) so[kk * NEED + q] = r[q];
-                if (counts) counts[base + kk] = (uint8_t)NEED;
-            }
-            if (slow) {
-                const uint32_t sp = atomicAdd(&nslow_tile, 1u);
-                if (sp < kSlowPerTile) slow_list[t * kSlowPerTile + sp] = kk;
-            }
+            lk.resolve(win[kq], h[k], lo[kq], bc[kq], ws[kq], (uint32_t)(tid + k * kLkThreads), nag, ag[wv], so, cnt_tile,
+                       defer);
         }
         }  // halves
         LK_T(t4, nag);
         // second windows, one listed key per lane (the list is this wave's own LDS rows)
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         for (uint32_t j = lane; j < (nag < AG ? nag : AG); j += 64)
-            finish2(load16(ag[wv][0][j]), ag[wv][1][j], ag[wv][2][j], so, counts ? counts + base : nullptr,
-                    &nslow_tile, slow_list + t * kSlowPerTile);
+            lk.finish2(lk.load16(ag[wv][0][j]), ag[wv][1][j], ag[wv][2][j], so, cnt_tile, defer);
         LK_T(t5a, nag);
         __syncthreads();
         LK_T(t5, tid);
@@ -1130,6 +1180,164 @@ __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4)))
             }
         }
     }
+}
+
+// ---- The sorted-tile lean kernel (the C2 default at 256 threads; RP_LOOKUP_SORT = 0 | 256 | 512 |
+// 1024 threads). The lean
+// kernel's index load holds 64 unrelated hashes per wave instruction, so every lane costs an
+// L1 -> L2 request. Here a tile of 8 * THREADS keys is ordered by its top hash bits with a
+// counting sort in LDS before the trips, and the ordered slots are dealt to lanes so that one
+// wave instruction holds 64 consecutive slots: neighbouring lanes share index lines (4,096
+// 128-B lines of 8-B group records at C2) and sometimes window lines
+// (tools/model_sorted_lines.py). Only which 64 keys share an instruction matters, not their
+// order inside it, so THREADS bins (8 keys a bin, 8 bins an instruction; the same shift for
+// every ring) share within 0.02 requests a key of what 4,096 bins do, and their counters are
+// scanned by one wave (4,096 bins, first built: 0.900 against 0.878 ms for the lean kernel).
+// Everything per key is the lean kernel's (LkStages); rows are addressed by the key's tile slot
+// kk, so results, counts and the deferred set do not depend on the order. Deferred keys go to
+// the lean kernel's 2,048-key logical tiles (list tile * TK / 2048 + kk / 2048, slot kk % 2048),
+// so k_lookupn_fix_tiles runs unchanged. Workgroups only meet at __syncthreads.
+// LDS: rows (12 B a key) over the key slice (<= 18 KB per 256 threads) and the ordered (h, kk)
+// pairs (8 B a key), both dead before the rows are written; + the 16-bit bin counters (two to
+// a word) and the per-wave lists.
+#ifdef RP_LK_PROF
+__device__ unsigned long long g_sk_prof[10];
+#endif
+constexpr int kSortDefault = 256;  // RP_LOOKUP_SORT when unset (0: the lean kernel; profiles/LOG.md)
+
+template <int THREADS, int NEED>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_lookupn_sorted(
+    const uint8_t* __restrict__ keys, uint64_t ntiles, CompactView cv, uint32_t* __restrict__ out,
+    uint8_t* __restrict__ counts, uint32_t* __restrict__ slow_list, uint32_t* __restrict__ slow_cnt) {
+    constexpr int LEN = 36, W4 = LEN / 4, KPL = 8, HS = 4;
+    constexpr int TK = THREADS * KPL;
+    constexpr int NW = THREADS / 64;
+    constexpr int SUB = TK / 2048;  // the lean kernel's logical tiles in one of these
+    constexpr int SK = TK * W4 / HS, SO = TK * NEED;
+    constexpr int BINS = THREADS;                 // 256 | 512 | 1024 bins on the top hash bits
+    constexpr int BSH = 32 - (BINS == 256 ? 8 : BINS == 512 ? 9 : 10);
+    constexpr int CW = BINS / 2;                  // counter words: two 16-bit bins each
+    constexpr int WPL = CW / 64;                  // counter words a lane of the scanning wave takes
+    static_assert(THREADS == 256 || THREADS == 512 || THREADS == 1024, "whole 2,048-key logical tiles, 13-bit slots, 16-bit bin counters");
+    static_assert(2 * TK <= SO && SK <= SO, "the ordered pairs and the key slice fit under the rows");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SO];
+    __shared__ uint32_t ag[NW][3][kLkAG];  // per-wave second-window list (LkStages::resolve)
+    __shared__ uint32_t bins[CW];
+    __shared__ uint32_t nslow_sub[SUB];
+    uint32_t* const sk = lds;  // a slice of 128 keys a wave
+    uint32_t* const so = lds;
+    u32x2* const pairs = reinterpret_cast<u32x2*>(lds);  // TK x (h, kk)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const LkStages<NEED, 13> lk(cv);
+#ifdef RP_LK_PROF
+    uint64_t pa[6] = {0, 0, 0, 0, 0, 0}, ntl = 0;
+#endif
+    if (tid < CW) bins[tid] = 0;
+    if (tid < SUB) nslow_sub[tid] = 0;
+    for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const uint64_t base = t * TK;
+        uint32_t h[KPL], kk[KPL];
+        LK_T(t0, tid);
+        // each wave stages and hashes its own 512 keys (tile slots wv * 512 + lane + 64 k): no
+        // workgroup barrier until the counts
+        lk_key_stage<64, KPL, HS, true>(keys + (base + (uint64_t)wv * 512) * LEN, sk + wv * (SK / NW), lane, h, [] {}, [] {});
+        LK_T(t1, h[KPL - 1]);
+        // rank in the bin: one LDS atomic per key (its half of the counter word)
+        uint32_t rank[KPL];
+#pragma unroll
+        for (int k = 0; k < KPL; k++) {
+            const uint32_t b = h[k] >> BSH, sh = (b & 1u) * 16u;
+            rank[k] = (atomicAdd(&bins[b >> 1], 1u << sh) >> sh) & 0xFFFFu;
+        }
+        __syncthreads();  // the counts are whole, and the last key slice is hashed
+        if (wv == 0) {  // exclusive scan of the bin counts in place, by one wave: bin starts
+            uint32_t c[WPL], sum = 0;
+#pragma unroll
+            for (int i = 0; i < WPL; i++) {
+                c[i] = bins[lane * WPL + i];
+                sum += (c[i] & 0xFFFFu) + (c[i] >> 16);
+            }
+            uint32_t x = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t y = __shfl_up(x, o, 64);
+                if (lane >= o) x += y;
+            }
+            uint32_t run = x - sum;
+#pragma unroll
+            for (int i = 0; i < WPL; i++) {
+                const uint32_t a = run, b = run + (c[i] & 0xFFFFu);
+                run = b + (c[i] >> 16);
+                bins[lane * WPL + i] = a | (b << 16);  // starts <= TK <= 8192
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < KPL; k++) {
+            const uint32_t b = h[k] >> BSH, sh = (b & 1u) * 16u;
+            const uint32_t slot = ((bins[b >> 1] >> sh) & 0xFFFFu) + rank[k];
+            pairs[slot] = u32x2{h[k], (uint32_t)(wv * 512 + lane + 64 * k)};
+        }
+        __syncthreads();
+        // lane tid takes slots tid + k THREADS: a wave instruction holds 64 consecutive slots
+#pragma unroll
+        for (int k = 0; k < KPL; k++) {
+            const u32x2 p = pairs[tid + k * THREADS];
+            h[k] = p.x;
+            kk[k] = p.y;
+        }
+        if (tid < CW) bins[tid] = 0;  // for the next tile (the starts were read before the barrier above)
+        if (tid < SUB) nslow_sub[tid] = 0;
+        LK_T(t2, kk[KPL - 1]);
+        __syncthreads();  // the pairs are dead: the rows take their place
+        uint32_t nag = 0;  // wave-uniform length of this wave's list
+        uint8_t* const cnt_tile = counts ? counts + base : nullptr;
+        auto defer = [&](uint32_t k) {  // to the list of the key's 2,048-key logical tile
+            const uint32_t s = k >> 11;
+            const uint32_t sp = atomicAdd(&nslow_sub[s], 1u);
+            if (sp < kSlowPerTile) slow_list[(t * SUB + s) * kSlowPerTile + sp] = k & 2047u;
+        };
+        u32x2 rec[KPL];
+#pragma unroll
+        for (int k = 0; k < KPL; k++) rec[k] = lk.index_rec(h[k]);
+        uint32_t lo[KPL], bc[KPL], ws[KPL];
+        u32x4 win[KPL];
+#pragma unroll
+        for (int k = 0; k < KPL; k++) win[k] = lk.window(h[k], rec[k], lo[k], bc[k], ws[k]);
+        LK_T(t3, lo[KPL - 1]);
+#pragma unroll
+        for (int k = 0; k < KPL; k++) lk.resolve(win[k], h[k], lo[k], bc[k], ws[k], kk[k], nag, ag[wv], so, cnt_tile, defer);
+        LK_T(t4, nag);
+        // second windows, one listed key per lane (the list is this wave's own LDS rows)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (uint32_t j = lane; j < (nag < kLkAG ? nag : kLkAG); j += 64)
+            lk.finish2(lk.load16(ag[wv][0][j]), ag[wv][1][j], ag[wv][2][j], so, cnt_tile, defer);
+        LK_T(t5a, nag);
+        __syncthreads();
+        LK_T(t5, tid);
+        if (tid < SUB) slow_cnt[t * SUB + tid] = nslow_sub[tid];
+        u32x4* d4 = reinterpret_cast<u32x4*>(out + base * NEED);
+        const u32x4* s4 = reinterpret_cast<const u32x4*>(so);
+#pragma unroll
+        for (int k = tid; k < TK * NEED / 4; k += THREADS) __builtin_nontemporal_store(s4[k], d4 + k);
+        __syncthreads();
+#ifdef RP_LK_PROF
+        LK_T(t6, tid);
+        pa[0] += t1 - t0;
+        pa[1] += t2 - t1;
+        pa[2] += t3 - t2;
+        pa[3] += t4 - t3;
+        pa[4] += t5a - t4;
+        pa[5] += t6 - t5;
+        ntl += 1;
+#endif
+    }
+#ifdef RP_LK_PROF
+    if (lane == 0) {
+        for (int i = 0; i < 6; i++) atomicAdd(&g_sk_prof[i], (unsigned long long)pa[i]);
+        atomicAdd(&g_sk_prof[6], (unsigned long long)ntl);
+    }
+#endif
 }
 
 // ---- The wave-specialised lean kernel (round 6, A/B: RP_LOOKUP_WS). The lean kernel's waves run
@@ -2995,11 +3203,48 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
         // RP_LOOKUP_KPL / RP_LOOKUP_HALF (slices: 2, 4) override (A/B).
         int kpl = getenv("RP_LOOKUP_KPL") ? atoi(getenv("RP_LOOKUP_KPL")) : (need == 3 ? 8 : 4);
         if (kpl != 1 && kpl != 2 && !((kpl == 3 || kpl == 8) && need == 3)) kpl = 4;  // the instantiated tiles
-        if (n < (uint64_t)kLkThreads * kpl) kpl = 4;  // at least one whole tile
+        // The sorted-tile kernel (RP_LOOKUP_SORT = 256 (default) | 512 | 1024 threads, 0 = off): only where
+        // the lean <8, 3, 4> kernel runs by default (lookupN(3) over the hinted index, no other
+        // RP_LOOKUP_* shape knob). It takes the whole tiles of 8 x threads keys; the rest goes on
+        // to the lean kernel's 2,048-key tiles and the generic kernel as before, and one fix pass
+        // covers both (the sorted kernel defers into the same 2,048-key lists).
+        int sort_t = kSortDefault;
+        if (const char* e = getenv("RP_LOOKUP_SORT")) sort_t = atoi(e);
+        RP_REQUIRE(sort_t == 0 || sort_t == 256 || sort_t == 512 || sort_t == 1024, "RP_LOOKUP_SORT: one of 0, 256, 512, 1024");
+        if (need != 3 || !cv.idxh || cv.ablate != 0 || n < 8ull * (uint64_t)sort_t || getenv("RP_LOOKUP_KPL") ||
+            getenv("RP_LOOKUP_HALF") || getenv("RP_LOOKUP_LEAN") || getenv("RP_LOOKUP_STG") || getenv("RP_LOOKUP_LH") ||
+            getenv_flag("RP_LOOKUP_FUSEFIX"))
+            sort_t = 0;
+        const uint64_t stiles = sort_t ? n / (8ull * (uint64_t)sort_t) : 0;
+        const uint64_t s0 = stiles * 8ull * (uint64_t)sort_t;  // keys the sorted kernel takes
+        const uint64_t t0 = s0 / 2048;                         // their 2,048-key lists
+        if (!sort_t && n < (uint64_t)kLkThreads * kpl) kpl = 4;  // at least one whole tile
         const uint64_t TK = (uint64_t)kLkThreads * kpl;
-        const uint64_t ntiles = n / TK, done = ntiles * TK;
-        r.slow.reserve(ntiles * kSlowPerTile + 1);
-        r.nslow.reserve(ntiles + 1);
+        const uint64_t ntiles = (n - s0) / TK, done = s0 + ntiles * TK;
+        r.slow.reserve((t0 + ntiles) * kSlowPerTile + 1);
+        r.nslow.reserve(t0 + ntiles + 1);
+        // the lean kernel's share: the keys after the sorted tiles
+        const uint8_t* const lkeys = keys + s0 * 36;
+        uint32_t* const lout = out + s0 * W;
+        uint8_t* const lcounts = counts ? counts + s0 : nullptr;
+        uint32_t* const lslow = r.slow.p + t0 * kSlowPerTile;
+        uint32_t* const lnslow = r.nslow.p + t0;
+        if (stiles) {
+            // workgroups, tiles strided over them (2^26 C2 keys, profiles/sorted_tiles/grid_sweep.txt):
+            // 256 threads 0.842 ms at 4096 (2048: 0.877, 8192: 0.845, 12288: 0.850); 512 threads 0.890
+            // at 8192 (1024-4096: 0.93-0.95); 1024 threads 0.997 at 512-1024. RP_LOOKUP_GRID overrides (A/B).
+            const unsigned sg = grid_for(stiles, 1, (unsigned)env_pos("RP_LOOKUP_GRID", sort_t == 256 ? 4096u : sort_t == 512 ? 8192u : 1024u));
+#define RP_SORTED(T) \
+    hipLaunchKernelGGL((k_lookupn_sorted<T, 3>), dim3(sg), dim3(T), 0, st, keys, stiles, cv, out, counts, r.slow.p, r.nslow.p)
+            if (sort_t == 256)
+                RP_SORTED(256);
+            else if (sort_t == 512)
+                RP_SORTED(512);
+            else
+                RP_SORTED(1024);
+#undef RP_SORTED
+            RP_HIP(hipGetLastError());
+        }
         const bool lean = !(getenv("RP_LOOKUP_LEAN") && !strcmp(getenv("RP_LOOKUP_LEAN"), "0"));  // A/B: 0 = round-1 kernel
         // workgroups, tiles strided over them: the lean kernel at 4096 (4 rounds of the 1024 that
         // fit, 8 tiles each at C2) ran 0.905-0.911 ms against 0.926-0.930 at 2048 (3072: 0.917;
@@ -3019,38 +3264,38 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
 #define RP_COMPACT(KPL, NEED)                                                                                  \
     do {                                                                                                        \
         if (KPL == 8 && NEED == 3 && stg2 && stghs == 8 && lh == 1)                                             \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 8, false, 2, 1>), dim3(g), dim3(kLkThreads), 0, st, keys,  \
-                               ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                           \
+            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 8, false, 2, 1>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
+                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
         else if (KPL == 8 && NEED == 3 && stg2 && stghs == 8)                                                   \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 8, false, 2, 2>), dim3(g), dim3(kLkThreads), 0, st, keys,  \
-                               ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                           \
+            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 8, false, 2, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
+                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
         else if (KPL == 8 && NEED == 3 && stg2)                                                                 \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 2, 2>), dim3(g), dim3(kLkThreads), 0, st, keys,  \
-                               ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                           \
+            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 2, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
+                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
         else if (KPL == 8 && NEED == 3 && stg1 && lh == 2)                                                      \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 1, 2>), dim3(g), dim3(kLkThreads), 0, st, keys,  \
-                               ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                           \
+            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 1, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
+                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
         else if (KPL == 8 && NEED == 3 && lh == 2)                                                              \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 0, 2>), dim3(g), dim3(kLkThreads), 0, st, keys,  \
-                               ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                           \
+            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 0, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
+                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
         else if (KPL == 8 && NEED == 3 && stg1)                                                                 \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 1>), dim3(g), dim3(kLkThreads), 0, st, keys,     \
-                               ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                           \
+            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 1>), dim3(g), dim3(kLkThreads), 0, st, lkeys,    \
+                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
         else if (lean && half == 4 && KPL % 4 == 0 && fuse)                                                     \
             hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED, (KPL % 4 == 0 ? 4 : 1), true>), dim3(g), dim3(kLkThreads), \
-                               0, st, keys, ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);               \
+                               0, st, lkeys, ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);               \
         else if (lean && half == 4 && KPL % 4 == 0)                                                             \
             hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED, (KPL % 4 == 0 ? 4 : 1)>), dim3(g), dim3(kLkThreads), 0, \
-                               st, keys, ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                  \
+                               st, lkeys, ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                  \
         else if (lean && half == 2 && KPL % 2 == 0)                                                             \
             hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED, (KPL % 2 == 0 ? 2 : 1)>), dim3(g), dim3(kLkThreads), 0, \
-                               st, keys, ntiles, cv, out, counts, r.slow.p, r.nslow.p, fv, np);                  \
+                               st, lkeys, ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                  \
         else if (lean)                                                                                          \
-            hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED>), dim3(g), dim3(kLkThreads), 0, st, keys, ntiles, cv,  \
-                               out, counts, r.slow.p, r.nslow.p, fv, np);                                       \
+            hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED>), dim3(g), dim3(kLkThreads), 0, st, lkeys, ntiles, cv, \
+                               lout, lcounts, lslow, lnslow, fv, np);                                           \
         else                                                                                                    \
-            hipLaunchKernelGGL((k_lookupn_compact<KPL, NEED>), dim3(g), dim3(kLkThreads), 0, st, keys, ntiles,   \
-                               cv, out, counts, r.slow.p, r.nslow.p);                                           \
+            hipLaunchKernelGGL((k_lookupn_compact<KPL, NEED>), dim3(g), dim3(kLkThreads), 0, st, lkeys, ntiles,  \
+                               cv, lout, lcounts, lslow, lnslow);                                               \
     } while (0)
 #define RP_COMPACT_N(KPL)         \
     switch (need) {               \
@@ -3059,7 +3304,8 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
         case 3: RP_COMPACT(KPL, 3); break; \
         default: RP_COMPACT(KPL, 4); break; \
     }
-        if (kpl == 1) {
+        if (ntiles == 0) {  // the sorted kernel took every whole tile
+        } else if (kpl == 1) {
             RP_COMPACT_N(1);
         } else if (kpl == 2) {
             RP_COMPACT_N(2);
@@ -3074,10 +3320,10 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
         }
 #undef RP_COMPACT_N
 #undef RP_COMPACT
-        const uint64_t fthreads = ntiles * kSlowPerTile;
+        const uint64_t fthreads = (t0 + ntiles) * kSlowPerTile;  // (t0 > 0: TK is 2048, the lists are uniform)
         if (cv.ablate != 3 && !fuse)
             hipLaunchKernelGGL((k_lookupn_fix_tiles<CompactFixView>), dim3((unsigned)((fthreads + 255) / 256)),
-                               dim3(256), 0, st, keys, fv, np, W, out, counts, r.slow.p, r.nslow.p, ntiles,
+                               dim3(256), 0, st, keys, fv, np, W, out, counts, r.slow.p, r.nslow.p, t0 + ntiles,
                                (uint32_t)TK);
         RP_HIP(hipGetLastError());
 #ifdef RP_LK_PROF
@@ -3092,19 +3338,29 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
                     v[6], v[0] / nw, v[1] / nw, v[2] / nw, v[3] / nw, v[4] / nw, v[5] / nw);
             memset(v, 0, sizeof v);
             RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_lk_prof), v, sizeof v));
+            if (stiles) {
+                RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_sk_prof), sizeof v));
+                const double sw = (double)(v[6] ? v[6] : 1);
+                fprintf(stderr,
+                        "[rp] sorted<%d> phase cycles per wave-tile (%llu): keys+hash %.0f sort+deal %.0f idx+win-issue %.0f "
+                        "win1+loop %.0f finish2 %.0f barrier+store %.0f\n",
+                        sort_t, v[6], v[0] / sw, v[1] / sw, v[2] / sw, v[3] / sw, v[4] / sw, v[5] / sw);
+                memset(v, 0, sizeof v);
+                RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_sk_prof), v, sizeof v));
+            }
         }
 #endif
         if (getenv_flag("RP_LOOKUP_DEBUG")) {
-            std::vector<uint32_t> c(ntiles);
-            RP_HIP(hipMemcpyAsync(c.data(), r.nslow.p, 4 * ntiles, hipMemcpyDeviceToHost, st));
+            std::vector<uint32_t> c(t0 + ntiles);
+            RP_HIP(hipMemcpyAsync(c.data(), r.nslow.p, 4 * (t0 + ntiles), hipMemcpyDeviceToHost, st));
             RP_HIP(hipStreamSynchronize(st));
             uint64_t tot = 0, over = 0;
             for (uint32_t x : c) {
                 tot += x;
                 over += x > kSlowPerTile;
             }
-            fprintf(stderr, "[rp] compact lookupN: %llu keys, %llu deferred, %llu overflowed tiles (cb %u ob %u fsh %u)\n",
-                    (unsigned long long)done, (unsigned long long)tot, (unsigned long long)over, r.ccb, r.cob, r.cfsh);
+            fprintf(stderr, "[rp] compact lookupN: %llu keys, %llu deferred, %llu overflowed tiles (cb %u ob %u fsh %u sort %d)\n",
+                    (unsigned long long)done, (unsigned long long)tot, (unsigned long long)over, r.ccb, r.cob, r.cfsh, sort_t);
         }
         if (done < n)  // the partial last tile
             launch_lookupn_view(r.view(), keys + done * 36, nullptr, 36, nullptr, n - done, np, W, out + done * W,

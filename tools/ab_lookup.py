@@ -41,6 +41,10 @@ def main():
         "compact-kpl1/lookupN3": ({"RP_LOOKUP_LEAN": "0", "RP_LOOKUP_KPL": "1"}, 3),
         "lean-kpl4/lookupN3": ({"RP_LOOKUP_HALF": "0", "RP_LOOKUP_KPL": "4"}, 3),
         "default/lookupN3": ({}, 3),
+        "sort0/lookupN3": ({"RP_LOOKUP_SORT": "0"}, 3),
+        "sort256/lookupN3": ({"RP_LOOKUP_SORT": "256"}, 3),
+        "sort512/lookupN3": ({"RP_LOOKUP_SORT": "512"}, 3),
+        "sort1024/lookupN3": ({"RP_LOOKUP_SORT": "1024"}, 3),
         "stg1/lookupN3": ({"RP_LOOKUP_STG": "1"}, 3),
         "lh2/lookupN3": ({"RP_LOOKUP_LH": "2"}, 3),
         "stg2/lookupN3": ({"RP_LOOKUP_STG": "2"}, 3),
@@ -97,7 +101,7 @@ def main():
     }
     if a.only:
         variants = {k: v for k, v in variants.items() if k in a.only.split(",")}
-    knobs = ("RP_LOOKUP_HALF", "RP_LOOKUP_LEAN", "RP_LOOKUP_KPL", "RP_RING_LAYOUT", "RP_LOOKUP_ABLATE", "RP_RING_WIDE", "RP_LOOKUP_GRID", "RP_LOOKUP_OCC", "RP_LOOKUP_STG", "RP_LOOKUP_LH", "RP_LOOKUP_STGHS", "RP_LOOKUP_LDS", "RP_LOOKUP_LDS_GRID", "RP_LOOKUP_LDS_STG", "RP_LOOKUP_LDS_ABL", "RP_LOOKUP_WS", "RP_LOOKUP_WS_GRID", "RP_LOOKUP_WS_ABL")
+    knobs = ("RP_LOOKUP_HALF", "RP_LOOKUP_LEAN", "RP_LOOKUP_KPL", "RP_RING_LAYOUT", "RP_LOOKUP_ABLATE", "RP_RING_WIDE", "RP_LOOKUP_GRID", "RP_LOOKUP_OCC", "RP_LOOKUP_STG", "RP_LOOKUP_LH", "RP_LOOKUP_STGHS", "RP_LOOKUP_LDS", "RP_LOOKUP_LDS_GRID", "RP_LOOKUP_LDS_STG", "RP_LOOKUP_LDS_ABL", "RP_LOOKUP_WS", "RP_LOOKUP_WS_GRID", "RP_LOOKUP_WS_ABL", "RP_LOOKUP_SORT")
     times = {k: [] for k in variants}
     digests = {}
     for r in range(a.rounds + 1):

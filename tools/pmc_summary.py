@@ -20,7 +20,7 @@ def main():
     for f in glob.glob(os.path.join(d, "*", "run_counter_collection.csv")):
         for r in csv.DictReader(open(f)):
             k = r["Kernel_Name"]
-            if "k_lookupn_lean<8, 3, 4" in k or "k_lookupn_leanILi8ELi3ELi4E" in k:
+            if "k_lookupn_sorted<256, 3" in k or "k_lookupn_sortedILi256ELi3E" in k:
                 kk = "compact"
             elif "k_lookupn_probe<36, 2, 1>" in k:
                 kk = "hashonly"
@@ -37,7 +37,7 @@ def main():
     writes = c["WRITE_SIZE"] * 1024
     fixb = (fx.get("FETCH_SIZE", 0) + fx.get("WRITE_SIZE", 0)) * 1024
     out = {
-        "kernel": "k_lookupn_lean<8,3,4> (+ k_lookupn_fix_tiles)",
+        "kernel": "k_lookupn_sorted<256,3> (+ k_lookupn_fix_tiles)",
         "keys_per_launch": keys,
         "counters_per_launch": avg,
         "key_stream_bytes": stream,
@@ -49,7 +49,8 @@ def main():
         "l2_hit_rate": c["TCC_HIT_sum"] / (c["TCC_HIT_sum"] + c["TCC_MISS_sum"]),
         "l1_to_l2_read_requests_per_key": c["TCP_TCC_READ_REQ_sum"] / keys,
         "method": "separate rocprofv3 --pmc passes (FETCH_SIZE | WRITE_SIZE | TCC_HIT_sum,TCC_MISS_sum | "
-                  "TCC_EA0_RDREQ_sum | TCP_TCC_READ_REQ_sum) over tools/ab_lookup.py (tools/pmc_lookup.sh); "
+                  "TCC_EA0_RDREQ_sum | TCP_TCC_READ_REQ_sum, counters only, no tracing) over tools/ab_lookup.py "
+                  "(tools/pmc_lookup.sh); "
                   "FETCH_SIZE of the key stream doubled per the gfx950 correction, calibrated with the hash-only "
                   "ablation kernel whose FETCH_SIZE is exactly half of the 2.42 GB of keys.",
     }
