@@ -739,6 +739,31 @@ int rp_sim_routing(rp_sim *s, rp_ring *ring, const char *keys, const uint64_t *o
                    uint32_t *truth_owner);
 int rp_sim_routing_hashes(rp_sim *s, rp_ring *ring, const uint32_t *hashes, uint64_t n, const uint8_t *truth,
                           uint64_t *wrong, uint64_t *lost, uint32_t *key_wrong, uint32_t *truth_owner);
+/* Census of every member over the handle's views, on the handle's stream after the rounds queued
+ * so far. Observers O: the handle's nodes v with observe[v] != 0 (observe: uint8[N], global, by
+ * node id); observe NULL: every local node that is up now (the nodes rp_sim_checksums reports a
+ * checksum for). A node that is down may be observed explicitly: its view is kept. With st_v(a),
+ * inc_v(a), ring_v(a) node v's row for member a, the outputs, by member id and each nullable:
+ *   n_obs            |O|
+ *   status[a*4 + s]  #{v in O : st_v(a) = s}, s = alive, suspect, faulty, leave   [N*4]
+ *   in_ring[a]       #{v in O : ring_v(a)}                                       [N]
+ *   max_inc[a]       max over v in O of inc_v(a); INT64_MIN when O is empty       [N]
+ *   at_max[a]        #{v in O : inc_v(a) = ref[a]}                               [N]
+ *   behind[lv]       for v in O: #{a : inc_v(a) < ref[a]}; 0 outside O           [the handle's nodes]
+ * ref = max_ref[N] when given, else this call's own max_inc. No shard of a sharded simulator sees
+ * the global maximum: the host takes the element-wise max of the shards' max_inc and passes it
+ * back as max_ref (status, in_ring and at_max then add up over the shards). A sharded handle
+ * answers only at a round boundary (before stage 0), else RP_EINVAL. An empty shard or an empty O
+ * gives zeros and INT64_MIN. Host buffers, synchronous; the scratch belongs to the handle and is
+ * reused. The rows are not swept: the call reads every node's deviation bitmap ([W] words by
+ * address rank) and only the rows whose bit is set, because a clear bit means the row is still
+ * (alive, inc0[a], in the ring). Three places keep that: the bootstrap clears the bitmap
+ * (k_sim_init), every row update sets the bit next to its store (block_apply), and a join
+ * rebuilds the joiner's bitmap by the same rule (k_join_view); no other code writes a row.
+ * at_max and behind cost a second pass over the bitmap, made only when one of them is asked for.
+ * RP_CENSUS_ROWS (read per call) sets the rows a workgroup covers. */
+int rp_sim_census(rp_sim *s, const uint8_t *observe, const int64_t *max_ref, uint32_t *n_obs, uint32_t *status,
+                  uint32_t *in_ring, int64_t *max_inc, uint32_t *at_max, uint32_t *behind);
 
 /* Stream-ordered copy between any host / device buffers (hipMemcpyDefault); NULL stream =
  * synchronous. Used by hosts that move sharded-simulator messages. */

@@ -151,6 +151,7 @@ SIGNATURES = {
     "rp_sim_ring_members": (_INT, [_P, _U32, _P]),
     "rp_sim_routing": (_INT, [_P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P, _P]),
     "rp_sim_routing_hashes": (_INT, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "rp_sim_census": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rp_members_defer_checksum": (_INT, [_P, _INT]),
     "rp_members_checksum_shard": (_INT, [_P, _U32, _U32, _U32]),
     "rp_members_checksum_history": (_INT, [_P, _P, _P, _U32, _P]),
@@ -1304,6 +1305,9 @@ def _sim_create(names, inc0, dead, seed, suspicion_rounds, now0, device, bounds,
     return h
 
 
+_CENSUS_FIELDS = ("observers", "status", "in_ring", "max_inc", "at_max", "behind")
+
+
 class GossipSim:
     """N full ringpop nodes advanced in the deterministic gossip round model on the device
     (DESIGN.md §SWIM round model; oracle/orc_sim.c restates it on the CPU). events: scenario
@@ -1401,6 +1405,46 @@ class GossipSim:
         else:
             check(lib().rp_sim_routing(self._h, ring._h, blob.ctypes.data, _ptr(off), stride, k, *outs))
         return res
+
+    def census(self, observe=None, max_ref=None, want=_CENSUS_FIELDS):
+        """Census of every member over this handle's views (rp_sim_census): {"observers": int,
+        "status": uint32 [N, 4] (alive, suspect, faulty, leave), "in_ring", "at_max": uint32 [N],
+        "max_inc": int64 [N], "behind": uint32 per node of the handle}, counted over the observers:
+        the handle's nodes v with observe[v] (bool[N] by node id; None: the nodes that are up).
+        at_max / behind compare with max_ref (int64[N]; None: this call's own max_inc). want: the
+        fields to compute (at_max and behind cost a second pass)."""
+        nl = getattr(self, "NL", self.N)
+        ob = None if observe is None else np.ascontiguousarray(np.asarray(observe) != 0, dtype=np.uint8)
+        if ob is not None and len(ob) != self.N:
+            raise ValueError("observe must have one entry per node")
+        mr = None if max_ref is None else np.ascontiguousarray(max_ref, dtype=np.int64)
+        if mr is not None and len(mr) != self.N:
+            raise ValueError("max_ref must have one entry per member")
+        n_obs = ctypes.c_uint32()
+        res = {"status": np.zeros((self.N, 4), dtype=np.uint32), "in_ring": np.zeros(self.N, dtype=np.uint32),
+               "max_inc": np.zeros(self.N, dtype=np.int64), "at_max": np.zeros(self.N, dtype=np.uint32),
+               "behind": np.zeros(nl, dtype=np.uint32)}
+        res = {k: v for k, v in res.items() if k in want}
+        # (an empty shard's `behind` has no storage to point to)
+        outs = [res[k].ctypes.data if k in res and res[k].size else None for k in _CENSUS_FIELDS[1:]]
+        check(lib().rp_sim_census(self._h, _ptr(ob), _ptr(mr), ctypes.byref(n_obs), *outs))
+        res["observers"] = n_obs.value
+        return res
+
+
+def census_reduce(parts):
+    """One census from the shards' (GossipSim.census results in shard order): valid only when
+    every part was taken with the same max_ref (no shard's own max_inc is the global one)."""
+    parts = list(parts)
+    res = {"observers": sum(int(p["observers"]) for p in parts)}
+    for k in ("status", "in_ring", "at_max"):
+        if all(k in p for p in parts):
+            res[k] = np.sum([p[k] for p in parts], axis=0, dtype=np.uint32)
+    if all("max_inc" in p for p in parts):
+        res["max_inc"] = np.max([p["max_inc"] for p in parts], axis=0)
+    if all("behind" in p for p in parts):
+        res["behind"] = np.concatenate([p["behind"] for p in parts])
+    return res
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1519,6 +1563,7 @@ class SimShard:
 
     ring_members = GossipSim.ring_members
     routing = GossipSim.routing
+    census = GossipSim.census
 
 
 def conv_reduce(parts):
@@ -1637,6 +1682,13 @@ class ShardedGossipSim:
                 "lost": np.concatenate([p["lost"] for p in parts]),
                 "key_wrong": sum((p["key_wrong"] for p in parts[1:]), parts[0]["key_wrong"].copy()),
                 "truth_owner": parts[0]["truth_owner"]}
+
+    def census(self, observe=None):
+        """GossipSim.census over the shards, in two phases: the element-wise max of the shards'
+        max_inc, then every shard against it (census_reduce). observe None: each shard's own
+        default, together the unsharded one (every handle holds the global dead[])."""
+        ref = np.max([s.census(observe, want=("max_inc",))["max_inc"] for s in self.shards], axis=0)
+        return census_reduce([s.census(observe, max_ref=ref) for s in self.shards])
 
 
 class _DeviceBytes:
@@ -1880,6 +1932,26 @@ class DistGossipSim:
         c = sum(self._allgather(self.shard.counters().astype(np.int64)))
         c[7] = self.shard.counters()[7]
         return dict(zip(_COUNTER_NAMES, (int(x) for x in c)))
+
+    def _allreduce(self, arr, op):
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(arr).astype(np.int64))
+        if self.xchg.on_device:
+            t = t.to(self.xchg.device)
+        self.dist.all_reduce(t, op=op, group=self.group)
+        return t.cpu().numpy()
+
+    def census(self, observe=None):
+        """ShardedGossipSim.census across the ranks: max_inc all-reduced (MAX) into the reference,
+        then observers, status, in_ring and at_max all-reduced (SUM). behind stays this rank's."""
+        ops = self.dist.ReduceOp
+        ref = self._allreduce(self.shard.census(observe, want=("max_inc",))["max_inc"], ops.MAX)
+        part = self.shard.census(observe, max_ref=ref)
+        res = {"max_inc": ref, "behind": part["behind"],
+               "observers": int(self._allreduce(np.array([part["observers"]]), ops.SUM)[0])}
+        for k in ("status", "in_ring", "at_max"):
+            res[k] = self._allreduce(part[k], ops.SUM).astype(np.uint32)
+        return res
 
 
 # ------------------------------------------------------------------ gossip wire bodies

@@ -3305,6 +3305,204 @@ __global__ void k_sim_truth(const uint8_t* __restrict__ st, const uint8_t* __res
     truth[a] = (!dead[a] && (st[(uint64_t)a * N + a] & ST_MASK) != ST_LEAVE) ? IN_RING : 0;
 }
 
+// ---- rp_sim_census ----
+// A census of every member over the observed views without sweeping the rows: a clear deviation
+// bit means the row is still (alive, inc0, in ring) (k_sim_init, block_apply and k_join_view are
+// the only writers of a row, and each keeps the bit), so the passes read the NL x W bitmap words
+// and gather only the rows whose bit is set. Everything accumulates by address rank, as the
+// bitmap is laid out; k_census_ref and k_census_finish convert to member ids through sorted[].
+// A workgroup of kCsThreads owns a column tile of kCsWords bitmap words (kCsRanks ranks) and a
+// slab of rows; 16 lanes read one row's segment, so it covers kCsRowsStep rows a step. No
+// workgroup waits for another.
+constexpr uint32_t kCsThreads = 256, kCsWords = 16, kCsRanks = kCsWords * 32, kCsRowsStep = kCsThreads / kCsWords,
+                   kCsUnroll = 4;
+
+struct CensusDev {
+    const uint8_t* obs;  // [NL] 1 = the local node observes
+    uint32_t n_obs;
+    uint32_t rows;       // rows per slab
+    uint32_t ntiles;     // column tiles: workgroup b owns tile b % ntiles of slab b / ntiles
+    // by address rank
+    uint32_t* cnt;       // [N*4] deviated observers' rows per status
+    uint32_t* ring;      // [N]   deviated observers' rows in the ring
+    int64_t* mx;         // [N]   max incarnation over deviated observers' rows
+    uint32_t* clear;     // [N]   C(k): observers whose bit k is clear
+    int64_t* ref;        // [N]   the reference incarnation
+    uint8_t* low0;       // [N]   inc0 < ref
+    uint32_t* at;        // [N]   deviated observers' rows with inc == ref
+    uint32_t* acc;       // [NL]  per row: sum over its deviated entries of [inc < ref] - [inc0 < ref]
+    uint32_t* nlow;      // [1]   B = #{k : inc0 < ref}
+    const int64_t* max_ref;  // [N] by member id, or null
+    // by member id (by local node: behind)
+    uint32_t *o_status, *o_ring, *o_at, *o_behind;
+    int64_t* o_max;
+};
+
+// this workgroup's tile and rows; the word a thread reads in each of its rows (W when past the end)
+struct CensusTile {
+    uint32_t k0, r0, r1, w, sub;
+    uint32_t wmask;  // the word's valid bits (the last word of a bitmap row is partly filled)
+};
+__device__ __forceinline__ CensusTile census_tile(const SimDev& S, const CensusDev& C) {
+    CensusTile T;
+    const uint32_t tile = blockIdx.x % C.ntiles, slab = blockIdx.x / C.ntiles;
+    T.k0 = tile * kCsRanks;
+    T.r0 = (uint32_t)min((uint64_t)slab * C.rows, (uint64_t)S.NL);
+    T.r1 = (uint32_t)min((uint64_t)T.r0 + C.rows, (uint64_t)S.NL);
+    T.sub = threadIdx.x / kCsWords;
+    const uint32_t w = tile * kCsWords + threadIdx.x % kCsWords;
+    T.w = w < S.W ? w : S.W;
+    const uint32_t left = w < S.W ? S.N - w * 32u : 0u;  // ranks from this word's first on
+    T.wmask = left >= 32u ? 0xFFFFFFFFu : (1u << left) - 1u;
+    return T;
+}
+// the thread's deviation word of row r: 0 past the slab, outside O, or past the bitmap's last word
+__device__ __forceinline__ uint32_t census_word(const SimDev& S, const CensusDev& C, const CensusTile& T, uint32_t r) {
+    if (r >= T.r1 || T.w >= S.W || !C.obs[r]) return 0u;
+    return S.dev[(uint64_t)r * S.W + T.w] & T.wmask;
+}
+
+__global__ __launch_bounds__(256) void k_census_clear(SimDev S, CensusDev C) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < max(S.N, S.NL); i += gridDim.x * blockDim.x) {
+        if (i < S.N) {
+            for (uint32_t s = 0; s < 4; s++) C.cnt[4ull * i + s] = 0;
+            C.ring[i] = 0;
+            C.mx[i] = INT64_MIN;
+            C.at[i] = 0;
+        }
+        if (i < S.NL) C.acc[i] = 0;
+        if (i == 0) C.nlow[0] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kCsThreads) void k_census_count(SimDev S, CensusDev C) {
+    __shared__ uint32_t l_cnt[kCsRanks * 4];
+    __shared__ uint32_t l_ring[kCsRanks];
+    __shared__ long long l_mx[kCsRanks];
+    __shared__ uint32_t l_a[kCsRanks];  // sorted[] of the tile's ranks
+    const CensusTile T = census_tile(S, C);
+    for (uint32_t i = threadIdx.x; i < kCsRanks; i += kCsThreads) {
+        for (uint32_t s = 0; s < 4; s++) l_cnt[4 * i + s] = 0;
+        l_ring[i] = 0;
+        l_mx[i] = INT64_MIN;
+        l_a[i] = T.k0 + i < S.N ? S.sorted[T.k0 + i] : 0u;
+    }
+    __syncthreads();
+    if (T.w < S.W) {
+        const uint32_t kl0 = (threadIdx.x % kCsWords) * 32u;
+        for (uint32_t rb = T.r0 + T.sub; rb < T.r1; rb += kCsRowsStep * kCsUnroll) {
+            uint32_t word[kCsUnroll];  // the steps' words first: most are zero, the loads overlap
+            for (uint32_t u = 0; u < kCsUnroll; u++) word[u] = census_word(S, C, T, rb + u * kCsRowsStep);
+            for (uint32_t u = 0; u < kCsUnroll; u++) {
+                uint32_t bits = word[u];
+                const uint64_t row = (uint64_t)(rb + u * kCsRowsStep) * S.N;
+                while (bits) {
+                    const uint32_t kl = kl0 + (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1;
+                    const uint32_t a = l_a[kl];
+                    const uint8_t st = S.st[row + a];
+                    const long long x = S.inc[row + a];
+                    atomicAdd(&l_cnt[4 * kl + (st & ST_MASK)], 1u);
+                    if (st & IN_RING) atomicAdd(&l_ring[kl], 1u);
+                    __hip_atomic_fetch_max(&l_mx[kl], x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kCsRanks; i += kCsThreads) {
+        const uint32_t k = T.k0 + i;
+        if (k >= S.N) break;
+        uint32_t any = 0;
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t c = l_cnt[4 * i + s];
+            any |= c;
+            if (c) atomicAdd(&C.cnt[4ull * k + s], c);
+        }
+        if (!any) continue;  // no deviated row of this slab at rank k
+        if (l_ring[i]) atomicAdd(&C.ring[k], l_ring[i]);
+        __hip_atomic_fetch_max(reinterpret_cast<long long*>(&C.mx[k]), l_mx[i], __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// One thread per rank: the clear-bit observers join the deviated ones; the first outputs by
+// member id; ref, [inc0 < ref] and their count B for the second pass.
+__global__ __launch_bounds__(256) void k_census_ref(SimDev S, CensusDev C) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t low = 0;
+    if (k < S.N) {
+        const uint32_t a = S.sorted[k];
+        uint32_t c[4], d = 0;
+        for (uint32_t s = 0; s < 4; s++) d += c[s] = C.cnt[4ull * k + s];
+        const uint32_t clear = C.n_obs - d;  // D(k) = d: every deviated row has exactly one status
+        const int64_t i0 = S.inc0[a];
+        int64_t mx = C.mx[k];
+        if (clear && i0 > mx) mx = i0;
+        c[ST_ALIVE] += clear;
+        for (uint32_t s = 0; s < 4; s++) C.o_status[4ull * a + s] = c[s];
+        C.o_ring[a] = C.ring[k] + clear;
+        C.o_max[a] = mx;
+        const int64_t ref = C.max_ref ? C.max_ref[a] : mx;
+        C.clear[k] = clear;
+        C.ref[k] = ref;
+        low = i0 < ref ? 1u : 0u;
+        C.low0[k] = (uint8_t)low;
+    }
+    const uint32_t n = (uint32_t)__builtin_popcountll(__ballot(low != 0));
+    if (n && (threadIdx.x & 63u) == 0) atomicAdd(C.nlow, n);
+}
+
+__global__ __launch_bounds__(kCsThreads) void k_census_behind(SimDev S, CensusDev C) {
+    __shared__ long long l_ref[kCsRanks];
+    __shared__ uint32_t l_at[kCsRanks];
+    __shared__ uint32_t l_a[kCsRanks];
+    __shared__ uint8_t l_low0[kCsRanks];
+    const CensusTile T = census_tile(S, C);
+    for (uint32_t i = threadIdx.x; i < kCsRanks; i += kCsThreads) {
+        const bool in = T.k0 + i < S.N;
+        l_ref[i] = in ? C.ref[T.k0 + i] : 0;
+        l_low0[i] = in ? C.low0[T.k0 + i] : 0;
+        l_a[i] = in ? S.sorted[T.k0 + i] : 0u;
+        l_at[i] = 0;
+    }
+    __syncthreads();
+    const uint32_t kl0 = (threadIdx.x % kCsWords) * 32u;
+    // (the bound is the same for the whole workgroup, so the 16 lanes of a row shuffle together)
+    for (uint32_t rb = T.r0; rb < T.r1; rb += kCsRowsStep * kCsUnroll) {
+        uint32_t word[kCsUnroll];
+        for (uint32_t u = 0; u < kCsUnroll; u++) word[u] = census_word(S, C, T, rb + T.sub + u * kCsRowsStep);
+        for (uint32_t u = 0; u < kCsUnroll; u++) {
+            const uint32_t r = rb + T.sub + u * kCsRowsStep;
+            uint32_t bits = word[u];
+            const uint64_t row = (uint64_t)r * S.N;
+            int32_t delta = 0;
+            while (bits) {
+                const uint32_t kl = kl0 + (uint32_t)__builtin_ctz(bits);
+                bits &= bits - 1;
+                const long long x = S.inc[row + l_a[kl]], ref = l_ref[kl];
+                if (x == ref) atomicAdd(&l_at[kl], 1u);
+                delta += (x < ref ? 1 : 0) - (int32_t)l_low0[kl];
+            }
+            for (uint32_t m = kCsWords / 2; m; m >>= 1) delta += __shfl_xor(delta, (int)m, (int)kCsWords);
+            // (a non-zero sum comes from a word that was read, so r is a row of the slab)
+            if (delta && threadIdx.x % kCsWords == 0) atomicAdd(&C.acc[r], (uint32_t)delta);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kCsRanks; i += kCsThreads)
+        if (T.k0 + i < S.N && l_at[i]) atomicAdd(&C.at[T.k0 + i], l_at[i]);
+}
+
+__global__ __launch_bounds__(256) void k_census_finish(SimDev S, CensusDev C) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < S.N) {
+        const uint32_t a = S.sorted[i];
+        C.o_at[a] = C.at[i] + (S.inc0[a] == C.ref[i] ? C.clear[i] : 0u);
+    }
+    if (i < S.NL) C.o_behind[i] = C.obs[i] ? C.nlow[0] + C.acc[i] : 0u;
+}
+
 __global__ void k_sim_init(SimDev S) {
     const uint64_t NN = (uint64_t)S.NL * S.N;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < NN; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -3467,6 +3665,12 @@ struct Sim {
     DevBuf<uint32_t> rt_col, rt_u32;
     DevBuf<uint8_t> rt_truth, rt_keys;
     DevBuf<uint64_t> rt_off, rt_u64;
+    // rp_sim_census: the observer mask, the rank-ordered accumulators and the outputs' device
+    // copies (CensusDev), sized at the first call; the host's mask
+    DevBuf<uint8_t> cs_u8;
+    DevBuf<uint32_t> cs_u32;
+    DevBuf<int64_t> cs_i64;
+    std::vector<uint8_t> cs_obs;
 
     uint32_t cus = 0;  // compute units of the device (first refresh)
     void refresh_checksums() {
@@ -4651,6 +4855,92 @@ int rp_sim_routing_hashes(rp_sim* s, rp_ring* ring, const uint32_t* hashes, uint
     return guard([&] {
         RP_REQUIRE(n == 0 || hashes, "sim_routing_hashes: null hash buffer");
         sim_routing(SM(s), ring, nullptr, nullptr, 0, hashes, n, truth, wrong, lost, key_wrong, truth_owner);
+    });
+}
+
+int rp_sim_census(rp_sim* s, const uint8_t* observe, const int64_t* max_ref, uint32_t* n_obs, uint32_t* status,
+                  uint32_t* in_ring, int64_t* max_inc, uint32_t* at_max, uint32_t* behind) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        RP_REQUIRE(S.G == 1 || S.next_stage == 0,
+                   "sim_census: a sharded handle answers at a round boundary (before stage 0)");
+        const uint32_t N = S.N, NL = S.NL;
+        S.cs_obs.resize(NL);
+        uint32_t no = 0;
+        for (uint32_t lv = 0; lv < NL; lv++)
+            no += S.cs_obs[lv] = (observe ? observe[S.v0 + lv] != 0 : !S.h_dead[S.v0 + lv]) ? 1 : 0;
+        if (n_obs) *n_obs = no;
+        if (no == 0) {  // (an empty shard too) nothing to index
+            if (status) std::fill(status, status + 4ull * N, 0u);
+            if (in_ring) std::fill(in_ring, in_ring + N, 0u);
+            if (max_inc) std::fill(max_inc, max_inc + N, INT64_MIN);
+            if (at_max) std::fill(at_max, at_max + N, 0u);
+            if (behind) std::fill(behind, behind + NL, 0u);
+            return;
+        }
+        RP_HIP(hipSetDevice(S.device));
+        if (S.cus == 0) {
+            int n = 0;
+            RP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, S.device));
+            S.cus = (uint32_t)(n > 0 ? n : 1);
+        }
+        S.cs_u8.reserve((uint64_t)NL + N);
+        S.cs_u32.reserve(13ull * N + 2ull * NL + 1);  // cnt 4, ring, clear, at | acc, nlow | o_status 4, o_ring, o_at | o_behind
+        S.cs_i64.reserve(4ull * N);
+        rp::CensusDev C{};
+        uint8_t* obs = S.cs_u8.p;
+        C.obs = obs;
+        C.low0 = obs + NL;
+        uint32_t* u = S.cs_u32.p;
+        C.cnt = u; u += 4ull * N;
+        C.ring = u; u += N;
+        C.clear = u; u += N;
+        C.at = u; u += N;
+        C.acc = u; u += NL;
+        C.nlow = u; u += 1;
+        C.o_status = u; u += 4ull * N;
+        C.o_ring = u; u += N;
+        C.o_at = u; u += N;
+        C.o_behind = u;
+        C.mx = S.cs_i64.p;
+        C.ref = C.mx + N;
+        int64_t* mref = C.ref + N;
+        C.o_max = mref + N;
+        C.n_obs = no;
+        // the grid: column tiles x row slabs, by default a few workgroups a CU (kCsPerCu), the slab
+        // a multiple of the rows a step; RP_CENSUS_ROWS sets the slab (tests: many and ragged slabs)
+        constexpr uint32_t kCsPerCu = 4;
+        C.ntiles = (S.d.W + rp::kCsWords - 1) / rp::kCsWords;
+        const uint64_t want_slabs = std::max<uint64_t>(1, ((uint64_t)kCsPerCu * S.cus + C.ntiles - 1) / C.ntiles);
+        uint64_t rows = (NL + want_slabs - 1) / want_slabs;
+        rows = (rows + rp::kCsRowsStep - 1) / rp::kCsRowsStep * rp::kCsRowsStep;
+        rows = rp::env_pos("RP_CENSUS_ROWS", rows);
+        const uint64_t max_slabs = 0x7FFFFFFFull / C.ntiles;
+        rows = std::max<uint64_t>(rows, (NL + max_slabs - 1) / max_slabs);
+        C.rows = (uint32_t)std::min<uint64_t>(rows, NL);
+        const unsigned grid = (unsigned)(C.ntiles * (((uint64_t)NL + C.rows - 1) / C.rows));
+        const unsigned flat = rp::grid_for(std::max(N, NL), 256, 1u << 24);
+        const bool second = at_max || behind;
+        RP_HIP(hipMemcpyAsync(obs, S.cs_obs.data(), NL, hipMemcpyHostToDevice, S.st));
+        if (max_ref) {
+            RP_HIP(hipMemcpyAsync(mref, max_ref, 8ull * N, hipMemcpyHostToDevice, S.st));
+            C.max_ref = mref;
+        }
+        hipLaunchKernelGGL(rp::k_census_clear, dim3(rp::grid_for(std::max(N, NL), 256, 1024)), dim3(256), 0, S.st, S.d,
+                           C);
+        hipLaunchKernelGGL(rp::k_census_count, dim3(grid), dim3(rp::kCsThreads), 0, S.st, S.d, C);
+        hipLaunchKernelGGL(rp::k_census_ref, dim3(rp::grid_for(N, 256, 1u << 24)), dim3(256), 0, S.st, S.d, C);
+        if (second) {
+            hipLaunchKernelGGL(rp::k_census_behind, dim3(grid), dim3(rp::kCsThreads), 0, S.st, S.d, C);
+            hipLaunchKernelGGL(rp::k_census_finish, dim3(flat), dim3(256), 0, S.st, S.d, C);
+        }
+        RP_HIP(hipGetLastError());
+        if (status) RP_HIP(hipMemcpyAsync(status, C.o_status, 16ull * N, hipMemcpyDeviceToHost, S.st));
+        if (in_ring) RP_HIP(hipMemcpyAsync(in_ring, C.o_ring, 4ull * N, hipMemcpyDeviceToHost, S.st));
+        if (max_inc) RP_HIP(hipMemcpyAsync(max_inc, C.o_max, 8ull * N, hipMemcpyDeviceToHost, S.st));
+        if (at_max) RP_HIP(hipMemcpyAsync(at_max, C.o_at, 4ull * N, hipMemcpyDeviceToHost, S.st));
+        if (behind) RP_HIP(hipMemcpyAsync(behind, C.o_behind, 4ull * NL, hipMemcpyDeviceToHost, S.st));
+        RP_HIP(hipStreamSynchronize(S.st));
     });
 }
 

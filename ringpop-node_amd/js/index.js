@@ -473,6 +473,18 @@ GossipSim.prototype.step = function step(rounds) { native.simStep(this._h, round
 GossipSim.prototype.round = function round() { return native.simRound(this._h); };
 GossipSim.prototype.checksums = function checksums() { return native.simChecksums(this._h, this.n); };
 GossipSim.prototype.view = function view(v) { return native.simView(this._h, v, this.n); };
+// Census of every member over all views (rp_sim_census): {observers, status: Uint32Array(4n) with
+// [a * 4 + s] the observers holding member a as alive / suspect / faulty / leave, inRing, atMax:
+// Uint32Array(n), maxInc: Float64Array(n) as view().inc, behind: Uint32Array(n) per node}.
+// observe: one truthy entry per observing node; omitted: every node that is up.
+GossipSim.prototype.census = function census(observe) {
+    var mask = null;
+    if (observe !== undefined && observe !== null) {
+        if (observe.length !== this.n) { throw new TypeError('observe must have one entry per node'); }
+        mask = Uint8Array.from(observe, function (x) { return x ? 1 : 0; });
+    }
+    return native.simCensus(this._h, this.n, mask);
+};
 GossipSim.prototype.converged = function converged() { return native.simConverged(this._h); };
 GossipSim.prototype.stats = function stats() { return native.simStats(this._h); };
 

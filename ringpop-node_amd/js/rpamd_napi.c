@@ -1472,6 +1472,47 @@ static napi_value js_sim_view(napi_env env, napi_callback_info info) {
     return out;
 }
 
+/* simCensus(handle, n, observe: Uint8Array(n) | null) -> {observers, status: Uint32Array(4n),
+ * inRing, atMax: Uint32Array(n), maxInc: Float64Array(n) (as simView's inc), behind: Uint32Array(n)} */
+static napi_value js_sim_census(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    handle_t *h = get_handle(env, argv[0], 3);
+    if (!h) return NULL;
+    uint32_t n = 0;
+    NAPI_OK(napi_get_value_uint32(env, argv[1], &n));
+    size_t no = 0;
+    const uint8_t *observe = (const uint8_t *)typed_data(env, argv[2], napi_uint8_array, &no);
+    napi_valuetype vt = napi_undefined;
+    napi_typeof(env, argv[2], &vt);
+    if ((vt != napi_null && vt != napi_undefined && !observe && n) || (observe && no != n)) {
+        napi_throw_type_error(env, NULL, "observe: a Uint8Array with one entry per node, or null");
+        return NULL;
+    }
+    void *sd = NULL, *rd = NULL, *ad = NULL, *bd = NULL, *md = NULL;
+    napi_value st = new_typed(env, napi_uint32_array, 4 * (size_t)n, 4, &sd);
+    napi_value ring = new_typed(env, napi_uint32_array, n, 4, &rd);
+    napi_value at = new_typed(env, napi_uint32_array, n, 4, &ad);
+    napi_value behind = new_typed(env, napi_uint32_array, n, 4, &bd);
+    napi_value mx = new_typed(env, napi_float64_array, n, 8, &md);
+    int64_t *i64 = (int64_t *)malloc(sizeof(int64_t) * (n ? n : 1));
+    uint32_t n_obs = 0;
+    int rc = rp_sim_census((rp_sim *)h->p, observe, NULL, &n_obs, (uint32_t *)sd, (uint32_t *)rd, i64, (uint32_t *)ad,
+                           (uint32_t *)bd);
+    for (uint32_t i = 0; rc == 0 && i < n; i++) ((double *)md)[i] = (double)i64[i];
+    free(i64);
+    RP_OK(rc);
+    napi_value out, nv;
+    napi_create_object(env, &out);
+    napi_create_uint32(env, n_obs, &nv);
+    napi_set_named_property(env, out, "observers", nv);
+    napi_set_named_property(env, out, "status", st);
+    napi_set_named_property(env, out, "inRing", ring);
+    napi_set_named_property(env, out, "maxInc", mx);
+    napi_set_named_property(env, out, "atMax", at);
+    napi_set_named_property(env, out, "behind", behind);
+    return out;
+}
+
 static napi_value js_sim_converged(napi_env env, napi_callback_info info) {
     ARGS(1);
     handle_t *h = get_handle(env, argv[0], 3);
@@ -1755,6 +1796,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringOwnerShare", NULL, js_ring_owner_share, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedRanges", NULL, js_ring_moved_ranges, NULL, NULL, NULL, napi_default, NULL},
         {"ringSnapDump", NULL, js_ring_snap_dump, NULL, NULL, NULL, napi_default, NULL},
+        {"simCensus", NULL, js_sim_census, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later);
     return exports;
