@@ -228,6 +228,30 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+class _KeySrc:
+    """The keys of one batch call, as the C ABI takes them: n caller hashes (hs), or n keys packed
+    into blob with offsets or a stride (HashRing._key_pack)."""
+
+    def __init__(self, n, blob=None, off=None, stride=0, hs=None):
+        self.n, self.blob, self.off, self.stride, self.hs = n, blob, off, stride, hs
+
+    @classmethod
+    def of_hashes(cls, hashes):
+        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
+        return cls(len(hs), hs=hs)
+
+    def both(self):
+        """(keys, off, stride, hashes) for an entry point that takes either."""
+        return None if self.blob is None else self.blob.ctypes.data, _ptr(self.off), self.stride, _ptr(self.hs)
+
+    def call(self, by_keys, by_hashes, handles, *rest):
+        """by_hashes(*handles, hashes, n, *rest) or by_keys(*handles, keys, off, stride, n, *rest)."""
+        if self.hs is not None:
+            check(by_hashes(*handles, self.hs.ctypes.data, self.n, *rest))
+        else:
+            check(by_keys(*handles, self.blob.ctypes.data, _ptr(self.off), self.stride, self.n, *rest))
+
+
 def gen_uuid_keys_dev(seed, k0, n, out_ptr, stream=None):
     """Fill a device buffer (>= 36*n bytes, 4-byte aligned) with the synthetic key stream."""
     check(lib().rp_gen_uuid_keys_dev(seed, k0, n, out_ptr, stream))
@@ -434,60 +458,51 @@ class HashRing:
         blob = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8)
         return blob, off, 0, len(bs)
 
+    def _key_src(self, keys):
+        """The keys as every batch entry point takes them: with a hashFunc their hashes (the
+        *_hashes entry points), else packed bytes."""
+        if self.hashFunc is not None:
+            return _KeySrc.of_hashes([self.hashFunc(k) & 0xFFFFFFFF for k in keys])
+        blob, off, stride, n = self._key_pack(keys)
+        return _KeySrc(n, blob, off, stride)
+
+    def _lookup(self, src):
+        out = np.empty(max(src.n, 1), dtype=np.uint32)
+        src.call(lib().rp_ring_lookup, lib().rp_ring_lookup_hashes, (self._h,), out.ctypes.data)
+        return out[:src.n]
+
+    def _lookupn(self, src, n):
+        out = np.empty((max(src.n, 1), max(int(n), 1)), dtype=np.uint32)
+        cnt = np.empty(max(src.n, 1), dtype=np.uint8)
+        src.call(lib().rp_ring_lookupn, lib().rp_ring_lookupn_hashes, (self._h,), int(n), out.ctypes.data,
+                 cnt.ctypes.data)
+        return out[:src.n], cnt[:src.n]
+
     def lookup_ids(self, keys):
         """Batched lookup: owner ids (NULL_ID = null)."""
-        if self.hashFunc is not None:
-            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
-            return self.lookup_hashes(hs)
-        blob, off, stride, n = self._key_pack(keys)
-        out = np.empty(max(n, 1), dtype=np.uint32)
-        check(lib().rp_ring_lookup(self._h, blob.ctypes.data, _ptr(off), stride, n, out.ctypes.data))
-        return out[:n]
+        return self._lookup(self._key_src(keys))
 
     def lookupn_ids(self, keys, n):
         """Batched lookupN: (owners[k, max(n,1)], counts[k])."""
-        if self.hashFunc is not None:
-            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
-            return self.lookupn_hashes(hs, n)
-        blob, off, stride, k = self._key_pack(keys)
-        w = max(int(n), 1)
-        out = np.empty((max(k, 1), w), dtype=np.uint32)
-        cnt = np.empty(max(k, 1), dtype=np.uint8)
-        check(lib().rp_ring_lookupn(self._h, blob.ctypes.data, _ptr(off), stride, k, int(n), out.ctypes.data,
-                                    cnt.ctypes.data))
-        return out[:k], cnt[:k]
+        return self._lookupn(self._key_src(keys), n)
 
     def lookup_hashes(self, hashes):
-        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
-        out = np.empty(max(len(hs), 1), dtype=np.uint32)
-        check(lib().rp_ring_lookup_hashes(self._h, hs.ctypes.data, len(hs), out.ctypes.data))
-        return out[:len(hs)]
+        return self._lookup(_KeySrc.of_hashes(hashes))
 
     def lookupn_hashes(self, hashes, n):
-        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
-        w = max(int(n), 1)
-        out = np.empty((max(len(hs), 1), w), dtype=np.uint32)
-        cnt = np.empty(max(len(hs), 1), dtype=np.uint8)
-        check(lib().rp_ring_lookupn_hashes(self._h, hs.ctypes.data, len(hs), int(n), out.ctypes.data,
-                                           cnt.ctypes.data))
-        return out[:len(hs)], cnt[:len(hs)]
+        return self._lookupn(_KeySrc.of_hashes(hashes), n)
 
     # -- keys grouped by owner: handleOrProxyAll (index.js:609-667) / lookupKeys (send.js:171-179)
     def group_ids(self, keys, self_id=NULL_ID):
         """(dests, group_off, perm): owners in first-seen order, group bounds, key indices."""
-        n = len(keys)
+        src = self._key_src(keys)
+        n = src.n
         dests = np.empty(max(n, 1), dtype=np.uint32)
         goff = np.empty(max(n, 1) + 1, dtype=np.uint32)
         perm = np.empty(max(n, 1), dtype=np.uint32)
         nd = ctypes.c_uint32()
-        if self.hashFunc is not None:
-            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
-            check(lib().rp_ring_group_hashes(self._h, hs.ctypes.data, n, self_id, dests.ctypes.data,
-                                             goff.ctypes.data, perm.ctypes.data, ctypes.byref(nd)))
-        else:
-            blob, off, stride, n = self._key_pack(keys)
-            check(lib().rp_ring_group_keys(self._h, blob.ctypes.data, _ptr(off), stride, n, self_id,
-                                           dests.ctypes.data, goff.ctypes.data, perm.ctypes.data, ctypes.byref(nd)))
+        src.call(lib().rp_ring_group_keys, lib().rp_ring_group_hashes, (self._h,), self_id, dests.ctypes.data,
+                 goff.ctypes.data, perm.ctypes.data, ctypes.byref(nd))
         k = nd.value
         return dests[:k], goff[:k + 1], perm[:n]
 
@@ -526,21 +541,13 @@ class HashRing:
         (NULL_ID padded). cap bounds the entries returned; `moved_count` holds the full count."""
         w = max(int(n), 1)
         cnt = ctypes.c_uint32()
-        if self.hashFunc is not None:
-            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
-            k = len(hs)
-        else:
-            blob, off, stride, k = self._key_pack(keys)
-        c = k if cap is None else min(int(cap), k)
+        src = self._key_src(keys)
+        c = src.n if cap is None else min(int(cap), src.n)
         idx = np.empty(max(c, 1), dtype=np.uint32)
         br = np.empty((max(c, 1), w), dtype=np.uint32)
         ar = np.empty((max(c, 1), w), dtype=np.uint32)
-        if self.hashFunc is not None:
-            check(lib().rp_ring_moved_hashes(self._h, before._h, hs.ctypes.data, k, int(n), c, idx.ctypes.data,
-                                             br.ctypes.data, ar.ctypes.data, ctypes.byref(cnt)))
-        else:
-            check(lib().rp_ring_moved_keys(self._h, before._h, blob.ctypes.data, _ptr(off), stride, k, int(n), c,
-                                           idx.ctypes.data, br.ctypes.data, ar.ctypes.data, ctypes.byref(cnt)))
+        src.call(lib().rp_ring_moved_keys, lib().rp_ring_moved_hashes, (self._h, before._h), int(n), c,
+                 idx.ctypes.data, br.ctypes.data, ar.ctypes.data, ctypes.byref(cnt))
         self.moved_count = cnt.value
         m = min(cnt.value, c)
         return idx[:m], br[:m], ar[:m]
@@ -568,12 +575,8 @@ class HashRing:
         (key, slot) ordered stream); `handoff_count` holds the full count."""
         w = max(int(n), 1)
         cnt, nd = ctypes.c_uint32(), ctypes.c_uint32()
-        if self.hashFunc is not None:
-            hs = np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
-            k = len(hs)
-        else:
-            blob, off, stride, k = self._key_pack(keys)
-        c = k * w if cap is None else min(int(cap), k * w)
+        ksrc = self._key_src(keys)
+        c = ksrc.n * w if cap is None else min(int(cap), ksrc.n * w)
         osrc = NULL_ID if only_src is None else int(only_src)
         bound = min(c, self.id_bound())
         dests = np.empty(max(bound, 1), dtype=np.uint32)
@@ -581,13 +584,9 @@ class HashRing:
         kidx = np.empty(max(c, 1), dtype=np.uint32)
         src = np.empty(max(c, 1), dtype=np.uint32)
         slot = np.empty(max(c, 1), dtype=np.uint8)
-        outs = (dests.ctypes.data, goff.ctypes.data, kidx.ctypes.data, src.ctypes.data, slot.ctypes.data,
-                ctypes.byref(nd), ctypes.byref(cnt))
-        if self.hashFunc is not None:
-            check(lib().rp_ring_handoff_hashes(self._h, before._h, hs.ctypes.data, k, int(n), osrc, c, *outs))
-        else:
-            check(lib().rp_ring_handoff(self._h, before._h, blob.ctypes.data, _ptr(off), stride, k, int(n), osrc, c,
-                                        *outs))
+        ksrc.call(lib().rp_ring_handoff, lib().rp_ring_handoff_hashes, (self._h, before._h), int(n), osrc, c,
+                  dests.ctypes.data, goff.ctypes.data, kidx.ctypes.data, src.ctypes.data, slot.ctypes.data,
+                  ctypes.byref(nd), ctypes.byref(cnt))
         self.handoff_count = cnt.value
         t, g = min(cnt.value, c), nd.value
         return dests[:g], goff[:g + 1], kidx[:t], src[:t], slot[:t]
@@ -624,7 +623,8 @@ class HashRing:
                                             truth_ptr, active_ptr, int(bool(accumulate)), wrong_ptr, lost_ptr,
                                             key_wrong_ptr, truth_owner_ptr, owners_ptr, stream))
 
-    def _route(self, blob, off, stride, hs, k, allowed, truth, active, col, owners):
+    def _route(self, src, allowed, truth, active, col, owners):
+        k = src.n
         allowed = np.ascontiguousarray(allowed, dtype=np.uint8)
         if allowed.ndim != 2:
             raise ValueError("allowed must be a [views, columns] matrix")
@@ -652,8 +652,7 @@ class HashRing:
                "key_wrong": np.zeros(k, dtype=np.uint32), "truth_owner": np.full(k, NULL_ID, dtype=np.uint32)}
         if owners:
             res["owners"] = np.full((k, nv), NULL_ID, dtype=np.uint32)
-        check(lib().rp_ring_route_views(self._h, None if hs is not None else blob.ctypes.data, _ptr(off), stride,
-                                        _ptr(hs), k, allowed.ctypes.data if nv else None, rs, 1, nv,
+        check(lib().rp_ring_route_views(self._h, *src.both(), k, allowed.ctypes.data if nv else None, rs, 1, nv,
                                         _ptr(colv), cap, _ptr(tr), _ptr(ac), 0,
                                         res["wrong"].ctypes.data if nv else None,
                                         res["lost"].ctypes.data if nv else None,
@@ -670,15 +669,10 @@ class HashRing:
         is not the truth's, "lost": uint64[views] keys sent to a server the truth does not allow,
         "key_wrong": uint32[keys] active views that disagree, "truth_owner": uint32[keys]} and, with
         owners=True, "owners": uint32[keys, views] (NULL_ID: null)."""
-        if self.hashFunc is not None:
-            return self.route_view_hashes(np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32),
-                                          allowed, truth, active, col, owners)
-        blob, off, stride, k = self._key_pack(keys)
-        return self._route(blob, off, stride, None, k, allowed, truth, active, col, owners)
+        return self._route(self._key_src(keys), allowed, truth, active, col, owners)
 
     def route_view_hashes(self, hashes, allowed, truth=None, active=None, col=None, owners=False):
-        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
-        return self._route(None, None, 0, hs, len(hs), allowed, truth, active, col, owners)
+        return self._route(_KeySrc.of_hashes(hashes), allowed, truth, active, col, owners)
 
     def routeViews(self, keys, views, truth=None):
         """views: a list of server-name lists (the servers each view's ring holds); truth: one more
@@ -711,21 +705,16 @@ class HashRing:
     def owner_load_ids(self, keys, n=1):
         """np.uint64[id_bound, max(n,1)]: [id, q] = how many keys have server id in slot q of their
         lookupN(key, n) row (q = 0: as primary)."""
-        if self.hashFunc is not None:
-            return self.owner_load_hashes(np.array([self.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32), n)
-        blob, off, stride, k = self._key_pack(keys)
-        cap, w = self.id_bound(), max(int(n), 1)
-        out = np.zeros((cap, w), dtype=np.uint64)
-        check(lib().rp_ring_owner_load(self._h, blob.ctypes.data, _ptr(off), stride, k, int(n), cap,
-                                       out.ctypes.data if cap else None))
-        return out
+        return self._owner_load(self._key_src(keys), n)
 
     def owner_load_hashes(self, hashes, n=1):
-        hs = np.ascontiguousarray(hashes, dtype=np.uint32)
+        return self._owner_load(_KeySrc.of_hashes(hashes), n)
+
+    def _owner_load(self, src, n):
         cap, w = self.id_bound(), max(int(n), 1)
         out = np.zeros((cap, w), dtype=np.uint64)
-        check(lib().rp_ring_owner_load_hashes(self._h, hs.ctypes.data, len(hs), int(n), cap,
-                                              out.ctypes.data if cap else None))
+        src.call(lib().rp_ring_owner_load, lib().rp_ring_owner_load_hashes, (self._h,), int(n), cap,
+                 out.ctypes.data if cap else None)
         return out
 
     def owner_load_dev(self, keys_ptr, n, nrep, load_ptr, id_cap, accumulate=False, stride=36, off_ptr=None,
@@ -1390,20 +1379,13 @@ class GossipSim:
         tr = None if truth is None else np.ascontiguousarray(np.asarray(truth) != 0, dtype=np.uint8)
         if tr is not None and len(tr) != self.N:
             raise ValueError("truth must have one entry per member")
-        hs = None
-        if ring.hashFunc is not None:
-            hs = np.array([ring.hashFunc(k) & 0xFFFFFFFF for k in keys], dtype=np.uint32)
-            k = len(hs)
-        else:
-            blob, off, stride, k = ring._key_pack(keys)
+        src = ring._key_src(keys)
+        k = src.n
         res = {"wrong": np.zeros(nl, dtype=np.uint64), "lost": np.zeros(nl, dtype=np.uint64),
                "key_wrong": np.zeros(k, dtype=np.uint32), "truth_owner": np.full(k, NULL_ID, dtype=np.uint32)}
-        outs = (_ptr(tr), res["wrong"].ctypes.data if nl else None, res["lost"].ctypes.data if nl else None,
-                res["key_wrong"].ctypes.data if k else None, res["truth_owner"].ctypes.data if k else None)
-        if hs is not None:
-            check(lib().rp_sim_routing_hashes(self._h, ring._h, hs.ctypes.data, k, *outs))
-        else:
-            check(lib().rp_sim_routing(self._h, ring._h, blob.ctypes.data, _ptr(off), stride, k, *outs))
+        src.call(lib().rp_sim_routing, lib().rp_sim_routing_hashes, (self._h, ring._h), _ptr(tr),
+                 res["wrong"].ctypes.data if nl else None, res["lost"].ctypes.data if nl else None,
+                 res["key_wrong"].ctypes.data if k else None, res["truth_owner"].ctypes.data if k else None)
         return res
 
     def census(self, observe=None, max_ref=None, want=_CENSUS_FIELDS):

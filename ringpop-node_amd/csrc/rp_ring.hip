@@ -2767,6 +2767,16 @@ struct Ring {
     }
 };
 
+// lookupN's replica count: the walk ends after np = min(nrep, server count) owners
+// (lib/ring/index.js:159-162) and a row has W = max(nrep, 1) slots, whatever the servers.
+struct Replicas {
+    int np;
+    uint32_t W;
+};
+static Replicas replicas(int32_t nrep, uint32_t servers) {
+    return {(int)std::min<int64_t>(nrep, servers), nrep > 1 ? (uint32_t)nrep : 1u};
+}
+
 static uint32_t ring_intern(Ring& r, const char* s, uint32_t n) {
     const uint32_t id = r.nt.intern(s, n);
     if (id >= r.in_ring.size()) {
@@ -3765,8 +3775,8 @@ static void moved_keys(Ring& r, const Snap& s, const uint8_t* keys, const uint64
         RP_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), st));
         return;
     }
-    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-    const int npb = (int)std::min<int64_t>(nrep, s.server_count), npa = (int)std::min<int64_t>(nrep, r.server_count);
+    const int npb = replicas(nrep, s.server_count).np;
+    const auto [npa, W] = replicas(nrep, r.server_count);
     const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const RingView bv = s.view(), av = r.view();
 #define RP_MOVED(MAXN, KPL, FIXED)                                                                                  \
@@ -4005,7 +4015,8 @@ static void handoff(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t*
                     const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap,
                     uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src, uint8_t* slot,
                     uint32_t* ndest, uint32_t* count, hipStream_t st, bool known_count) {
-    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const int npb = replicas(nrep, s.server_count).np;
+    const auto [npa, W] = replicas(nrep, r.server_count);
     const uint32_t id_bound = r.nt.size();
     RP_REQUIRE(nrep <= 8, "handoff: nrep is at most 8 (the rows are compared in registers)");
     RP_REQUIRE(n < (1ull << 32) && n * W < (1ull << 32), "handoff: n * max(nrep, 1) is at most 2^32-1 records");
@@ -4033,7 +4044,6 @@ static void handoff(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t*
     const int sort_bits = bits_for(id_bound);
     // the slots past the record count sort last (0xFF..: above every id in the sorted bits)
     if (m && !known_count) RP_HIP(hipMemsetAsync(ws.dst.p, 0xFF, 4ull * m, st));
-    const int npb = (int)std::min<int64_t>(nrep, s.server_count), npa = (int)std::min<int64_t>(nrep, r.server_count);
     const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const RingView bv = s.view(), av = r.view();
 #define RP_HANDOFF(MAXN, KPL, FIXED)                                                                                   \
@@ -4228,7 +4238,7 @@ static void owner_load_walk(LoadScratch& ls, uint64_t n, int32_t nrep, uint32_t 
                             hipStream_t st, Look&& look) {
     RP_REQUIRE(id_cap >= id_bound, "owner_load: id_cap is below the ring's id bound (rp_ring_id_bound)");
     RP_REQUIRE(id_cap == 0 || load, "owner_load: null load buffer");
-    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
+    const uint32_t W = replicas(nrep, 0).W;  // (the look callback walks with its ring's server count)
     const uint64_t bins = (uint64_t)id_cap * W;
     if (!accumulate && bins) RP_HIP(hipMemsetAsync(load, 0, bins * sizeof(uint64_t), st));
     if (n == 0 || !counts_anything || bins == 0) return;
@@ -4247,13 +4257,12 @@ static void owner_load_walk(LoadScratch& ls, uint64_t n, int32_t nrep, uint32_t 
 static void owner_load(Ring& r, LoadScratch& ls, const uint8_t* keys, const uint64_t* off, uint32_t stride,
                        const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t id_cap, int accumulate,
                        unsigned long long* load, hipStream_t st) {
-    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-    const int np = (int)std::min<int64_t>(nrep, r.server_count);  // lib/ring/index.js:159-162
+    const Replicas rep = replicas(nrep, r.server_count);
     owner_load_walk(ls, n, nrep, r.nt.size(), id_cap, r.M != 0, accumulate, load, r.device, st,
                     [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
                         launch_lookupn(r, hashes ? nullptr : (stride ? keys + k0 * stride : keys),
                                        (!hashes && !stride) ? off + k0 : nullptr, stride, hashes ? hashes + k0 : nullptr,
-                                       cnt, np, W, rows, nullptr, st);
+                                       cnt, rep.np, rep.W, rows, nullptr, st);
                     });
 }
 
@@ -4471,8 +4480,8 @@ static void moved_ranges(const RingView& bv, uint32_t sc_b, const RingView& av, 
     ws.mj.reserve(n);
     ws.flg.reserve(n);
     ws.tot.reserve(ntiles);
-    const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-    const int npb = (int)std::min<int64_t>(nrep, sc_b), npa = (int)std::min<int64_t>(nrep, sc_a);
+    const int npb = replicas(nrep, sc_b).np;
+    const auto [npa, W] = replicas(nrep, sc_a);
     hipLaunchKernelGGL(k_ranges_merge, dim3((n + kRngThreads - 1) / kRngThreads), dim3(kRngThreads), 0, st, bv, av,
                        ws.val.p, ws.mi.p, ws.mj.p);
     RP_HIP(hipGetLastError());
@@ -4505,7 +4514,7 @@ static void host_moved_ranges(const RingView& bv, uint32_t sc_b, const RingView&
     RP_REQUIRE(cap == 0 || (lo && hi), "moved_ranges: null range buffer");
     RP_REQUIRE((uint64_t)bv.M + av.M < (1ull << 31), "moved_ranges: more than 2^31 tokens");
     // io = [moved_hashes 2 | count 1 | pad 1 | lo c | hi c | before rows c*W | after rows c*W]
-    const uint64_t c = std::min<uint64_t>(cap, (uint64_t)bv.M + av.M + 1u), W = nrep > 1 ? (uint64_t)nrep : 1u;
+    const uint64_t c = std::min<uint64_t>(cap, (uint64_t)bv.M + av.M + 1u), W = replicas(nrep, sc_a).W;
     ws.use_on(st);
     ws.io.reserve(4 + c * (2 + 2 * W));
     uint32_t* dlo = ws.io.p + 4;
@@ -4827,6 +4836,58 @@ static rp::Ring& R(rp_ring* r) {
     return r->impl;
 }
 
+// The caller's keys, as every batch entry point takes them: key bytes (stride > 0: key i is
+// keys[i * stride .. + stride), else keys[off[i] .. off[i + 1])) or, from a caller hashFunc, the
+// key hashes. `hashed` says which form the entry point is; its buffer may still be null.
+struct KeySrc {
+    const char* keys;
+    const uint64_t* off;
+    uint32_t stride;
+    const uint32_t* hashes;
+    bool hashed;
+};
+static KeySrc key_bytes(const void* keys, const uint64_t* off, uint32_t stride) {
+    return {static_cast<const char*>(keys), off, stride, nullptr, false};
+}
+static KeySrc key_hashes(const uint32_t* hashes) { return {nullptr, nullptr, 0, hashes, true}; }
+
+// RP_EINVAL "<op>: null key buffer" (or "null hash buffer") unless n == 0 or the source is all
+// there. The lookups test their output buffer in the same breath (`rest`) and name no kind (`what`).
+static void require_keys(const char* op, const KeySrc& k, uint64_t n, bool rest = true, const char* what = nullptr) {
+    const bool given = k.hashed ? k.hashes != nullptr : (k.keys && (k.stride || k.off));
+    if (n == 0 || (given && rest)) return;
+    throw rp::Error(rp::RP_EINVAL, std::string(op) + ": null " + (what ? what : k.hashed ? "hash buffer" : "key buffer"));
+}
+
+// The host forms' staging, on r.st through the handle's buffers: hashes -> io_a; else the key
+// bytes -> io_keys (with 16 bytes of tail for the kernels' wide loads) and, without a stride, the
+// offsets -> io_off. n == 0 stages nothing. The pointers are what the rp:: passes take.
+struct DevKeys {
+    const uint8_t* dk;
+    const uint64_t* doff;
+    const uint32_t* dh;
+};
+static DevKeys stage_keys(rp::Ring& r, const KeySrc& k, uint64_t n) {
+    DevKeys d{nullptr, nullptr, nullptr};
+    if (n == 0) return d;
+    if (k.hashed) {
+        r.io_a.reserve(n);
+        RP_HIP(hipMemcpyAsync(r.io_a.p, k.hashes, n * 4, hipMemcpyHostToDevice, r.st));
+        d.dh = r.io_a.p;
+        return d;
+    }
+    const uint64_t bytes = k.stride ? n * k.stride : k.off[n];
+    r.io_keys.reserve(bytes + 16);
+    RP_HIP(hipMemcpyAsync(r.io_keys.p, k.keys, bytes, hipMemcpyHostToDevice, r.st));
+    d.dk = r.io_keys.p;
+    if (!k.stride) {
+        r.io_off.reserve(n + 1);
+        RP_HIP(hipMemcpyAsync(r.io_off.p, k.off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
+        d.doff = r.io_off.p;
+    }
+    return d;
+}
+
 extern "C" {
 
 int rp_ring_create(uint32_t replica_points, int device, rp_ring** out) {
@@ -5090,21 +5151,14 @@ int rp_ring_dump(rp_ring* h, uint32_t* tokens, uint32_t* owners, uint32_t cap) {
 
 // ---- lookups
 
-static int np_for(rp::Ring& r, int32_t nrep) {
-    int64_t n = nrep;
-    if (n > (int64_t)r.server_count) n = r.server_count;  // lib/ring/index.js:159-162
-    return (int)n;
-}
-
 int rp_ring_lookupn_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_off, uint32_t stride, uint64_t n,
                         int32_t nrep, uint32_t* d_owners, uint8_t* d_counts, void* stream) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (d_keys && d_owners && (stride || d_off)), "lookupn_dev: null buffer");
+        require_keys("lookupn_dev", key_bytes(d_keys, d_off, stride), n, d_owners != nullptr, "buffer");
         svc_stop(r);
-        const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-        rp::launch_lookupn(r, d_keys, d_off, stride, nullptr, n, np_for(r, nrep), W, d_owners, d_counts,
-                           rp::as_stream(stream));
+        const auto [np, W] = rp::replicas(nrep, r.server_count);
+        rp::launch_lookupn(r, d_keys, d_off, stride, nullptr, n, np, W, d_owners, d_counts, rp::as_stream(stream));
     });
 }
 
@@ -5112,7 +5166,7 @@ int rp_ring_lookup_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_off,
                        uint32_t* d_owners, void* stream) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (d_keys && d_owners && (stride || d_off)), "lookup_dev: null buffer");
+        require_keys("lookup_dev", key_bytes(d_keys, d_off, stride), n, d_owners != nullptr, "buffer");
         svc_stop(r);
         // lookup (:145-154) == a one-step walk, independent of getServerCount
         rp::launch_lookupn(r, d_keys, d_off, stride, nullptr, n, 1, 1, d_owners, nullptr, rp::as_stream(stream));
@@ -5123,11 +5177,10 @@ int rp_ring_lookupn_hashes_dev(rp_ring* h, const uint32_t* d_hashes, uint64_t n,
                                uint8_t* d_counts, void* stream) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (d_hashes && d_owners), "lookupn_hashes_dev: null buffer");
+        require_keys("lookupn_hashes_dev", key_hashes(d_hashes), n, d_owners != nullptr, "buffer");
         svc_stop(r);
-        const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-        rp::launch_lookupn(r, nullptr, nullptr, 0, d_hashes, n, np_for(r, nrep), W, d_owners, d_counts,
-                           rp::as_stream(stream));
+        const auto [np, W] = rp::replicas(nrep, r.server_count);
+        rp::launch_lookupn(r, nullptr, nullptr, 0, d_hashes, n, np, W, d_owners, d_counts, rp::as_stream(stream));
     });
 }
 
@@ -5263,37 +5316,21 @@ static bool svc_lookup(rp::Ring& r, const char* key, uint32_t len, const uint32_
     return true;
 }
 
-static void host_lookup(rp::Ring& r, const char* keys, const uint64_t* off, uint32_t stride, const uint32_t* hashes,
-                        uint64_t n, int np, uint32_t W, uint32_t* owners, uint8_t* counts) {
+static void host_lookup(rp::Ring& r, const KeySrc& k, uint64_t n, int np, uint32_t W, uint32_t* owners,
+                        uint8_t* counts) {
     if (n == 0) return;
-    if (n == 1 && (hashes ? svc_lookup(r, nullptr, 0, hashes, np, W, owners, counts)
-                          : svc_lookup(r, keys + (stride ? 0 : off[0]), (uint32_t)(stride ? stride : off[1] - off[0]),
-                                       nullptr, np, W, owners, counts)))
+    if (n == 1 && (k.hashed ? svc_lookup(r, nullptr, 0, k.hashes, np, W, owners, counts)
+                            : svc_lookup(r, k.keys + (k.stride ? 0 : k.off[0]),
+                                         (uint32_t)(k.stride ? k.stride : k.off[1] - k.off[0]), nullptr, np, W, owners,
+                                         counts)))
         return;
     rp::QuietScope quiet;  // the launch path: no resident service (this ring's or another's) meanwhile
     svc_stop(r);
-    if (!hashes && host_lookup_small(r, keys, off, stride, n, np, W, owners, counts)) return;
-    const uint8_t* dk = nullptr;
-    const uint64_t* doff = nullptr;
-    const uint32_t* dh = nullptr;
-    if (hashes) {
-        r.io_a.reserve(n);
-        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
-        dh = r.io_a.p;
-    } else {
-        const uint64_t bytes = stride ? n * stride : off[n];
-        r.io_keys.reserve(bytes + 16);
-        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
-        dk = r.io_keys.p;
-        if (!stride) {
-            r.io_off.reserve(n + 1);
-            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-            doff = r.io_off.p;
-        }
-    }
+    if (!k.hashed && host_lookup_small(r, k.keys, k.off, k.stride, n, np, W, owners, counts)) return;
+    const DevKeys d = stage_keys(r, k, n);
     r.io_b.reserve(n * W);
     if (counts) r.io_cnt.reserve(n);
-    rp::launch_lookupn(r, dk, doff, stride, dh, n, np, W, r.io_b.p, counts ? r.io_cnt.p : nullptr, r.st);
+    rp::launch_lookupn(r, d.dk, d.doff, k.stride, d.dh, n, np, W, r.io_b.p, counts ? r.io_cnt.p : nullptr, r.st);
     RP_HIP(hipMemcpyAsync(owners, r.io_b.p, n * W * 4, hipMemcpyDeviceToHost, r.st));
     if (counts) RP_HIP(hipMemcpyAsync(counts, r.io_cnt.p, n, hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
@@ -5312,8 +5349,9 @@ int rp_ring_service(rp_ring* h, uint32_t idle_ms) {
 int rp_ring_lookup(rp_ring* h, const char* keys, const uint64_t* off, uint32_t stride, uint64_t n, uint32_t* owners) {
     return guard_host([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (keys && owners && (stride || off)), "lookup: null buffer");
-        host_lookup(r, keys, off, stride, nullptr, n, 1, 1, owners, nullptr);
+        const KeySrc k = key_bytes(keys, off, stride);
+        require_keys("lookup", k, n, owners != nullptr, "buffer");
+        host_lookup(r, k, n, 1, 1, owners, nullptr);
     });
 }
 
@@ -5321,17 +5359,19 @@ int rp_ring_lookupn(rp_ring* h, const char* keys, const uint64_t* off, uint32_t 
                     uint32_t* owners, uint8_t* counts) {
     return guard_host([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (keys && owners && (stride || off)), "lookupn: null buffer");
-        host_lookup(r, keys, off, stride, nullptr, n, np_for(r, nrep), nrep > 1 ? (uint32_t)nrep : 1u, owners,
-                    counts);
+        const KeySrc k = key_bytes(keys, off, stride);
+        require_keys("lookupn", k, n, owners != nullptr, "buffer");
+        const auto [np, W] = rp::replicas(nrep, r.server_count);
+        host_lookup(r, k, n, np, W, owners, counts);
     });
 }
 
 int rp_ring_lookup_hashes(rp_ring* h, const uint32_t* hashes, uint64_t n, uint32_t* owners) {
     return guard_host([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (hashes && owners), "lookup_hashes: null buffer");
-        host_lookup(r, nullptr, nullptr, 0, hashes, n, 1, 1, owners, nullptr);
+        const KeySrc k = key_hashes(hashes);
+        require_keys("lookup_hashes", k, n, owners != nullptr, "buffer");
+        host_lookup(r, k, n, 1, 1, owners, nullptr);
     });
 }
 
@@ -5339,9 +5379,10 @@ int rp_ring_lookupn_hashes(rp_ring* h, const uint32_t* hashes, uint64_t n, int32
                            uint8_t* counts) {
     return guard_host([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (hashes && owners), "lookupn_hashes: null buffer");
-        host_lookup(r, nullptr, nullptr, 0, hashes, n, np_for(r, nrep), nrep > 1 ? (uint32_t)nrep : 1u, owners,
-                    counts);
+        const KeySrc k = key_hashes(hashes);
+        require_keys("lookupn_hashes", k, n, owners != nullptr, "buffer");
+        const auto [np, W] = rp::replicas(nrep, r.server_count);
+        host_lookup(r, k, n, np, W, owners, counts);
     });
 }
 
@@ -5353,7 +5394,7 @@ int rp_ring_group_keys_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_
     return guard([&] {
         rp::Ring& r = R(h);
         RP_REQUIRE(d_dests && d_group_off && d_perm && d_ndest, "group_keys_dev: null output buffer");
-        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "group_keys_dev: null key buffer");
+        require_keys("group_keys_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
         rp::group_keys(r, d_keys, d_off, stride, nullptr, n, self_id, d_dests, d_group_off, d_perm, d_ndest,
                        rp::as_stream(stream));
@@ -5361,28 +5402,11 @@ int rp_ring_group_keys_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_
 }
 
 // host-buffer forms: keys (or a caller hashFunc's key hashes) in, groups out
-static void host_group(rp::Ring& r, const char* keys, const uint64_t* off, uint32_t stride, const uint32_t* hashes,
-                       uint64_t n, uint32_t self_id, uint32_t* dests, uint32_t* goff, uint32_t* perm, uint32_t* ndest) {
+static void host_group(rp::Ring& r, const KeySrc& k, uint64_t n, uint32_t self_id, uint32_t* dests, uint32_t* goff,
+                       uint32_t* perm, uint32_t* ndest) {
     RP_REQUIRE(dests && goff && perm && ndest, "group_keys: null output buffer");
     svc_stop(r);
-    const uint8_t* dk = nullptr;
-    const uint64_t* doff = nullptr;
-    const uint32_t* dh = nullptr;
-    if (n && hashes) {
-        r.io_a.reserve(n);
-        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
-        dh = r.io_a.p;
-    } else if (n) {
-        const uint64_t bytes = stride ? n * stride : off[n];
-        r.io_keys.reserve(bytes + 16);
-        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
-        dk = r.io_keys.p;
-        if (!stride) {
-            r.io_off.reserve(n + 1);
-            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-            doff = r.io_off.p;
-        }
-    }
+    const DevKeys d = stage_keys(r, k, n);
     // io_b = [perm n | group_off n+1 | dests n | ndest 1]
     const uint64_t nn = n ? n : 1;
     r.io_b.reserve(3 * nn + 2);
@@ -5390,7 +5414,7 @@ static void host_group(rp::Ring& r, const char* keys, const uint64_t* off, uint3
     uint32_t* dgoff = dperm + nn;
     uint32_t* ddest = dgoff + nn + 1;
     uint32_t* dnd = ddest + nn;
-    rp::group_keys(r, dk, doff, stride, dh, n, self_id, ddest, dgoff, dperm, dnd, r.st);
+    rp::group_keys(r, d.dk, d.doff, k.stride, d.dh, n, self_id, ddest, dgoff, dperm, dnd, r.st);
     uint32_t nd = 0;
     RP_HIP(hipMemcpyAsync(&nd, dnd, 4, hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
@@ -5405,8 +5429,9 @@ int rp_ring_group_keys(rp_ring* h, const char* keys, const uint64_t* off, uint32
                        uint32_t self_id, uint32_t* dests, uint32_t* group_off, uint32_t* perm, uint32_t* ndest) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (keys && (stride || off)), "group_keys: null key buffer");
-        host_group(r, keys, off, stride, nullptr, n, self_id, dests, group_off, perm, ndest);
+        const KeySrc k = key_bytes(keys, off, stride);
+        require_keys("group_keys", k, n);
+        host_group(r, k, n, self_id, dests, group_off, perm, ndest);
     });
 }
 
@@ -5414,8 +5439,9 @@ int rp_ring_group_hashes(rp_ring* h, const uint32_t* hashes, uint64_t n, uint32_
                          uint32_t* group_off, uint32_t* perm, uint32_t* ndest) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || hashes, "group_hashes: null hash buffer");
-        host_group(r, nullptr, nullptr, 0, hashes, n, self_id, dests, group_off, perm, ndest);
+        const KeySrc k = key_hashes(hashes);
+        require_keys("group_hashes", k, n);
+        host_group(r, k, n, self_id, dests, group_off, perm, ndest);
     });
 }
 
@@ -5472,11 +5498,10 @@ int rp_ring_snap_lookupn_dev(rp_ring_snap* s, const uint8_t* d_keys, const uint6
                              uint64_t n, int32_t nrep, uint32_t* d_owners, uint8_t* d_counts, void* stream) {
     return guard([&] {
         RP_REQUIRE(s, "null snapshot handle");
-        RP_REQUIRE(n == 0 || (d_keys && d_owners && (stride || d_off)), "snap_lookupn_dev: null buffer");
+        require_keys("snap_lookupn_dev", key_bytes(d_keys, d_off, stride), n, d_owners != nullptr, "buffer");
         if (n == 0) return;
         RP_HIP(hipSetDevice(s->impl.device));
-        const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-        const int np = (int)std::min<int64_t>(nrep, s->impl.server_count);  // lib/ring/index.js:159-162
+        const auto [np, W] = rp::replicas(nrep, s->impl.server_count);
         rp::launch_lookupn_view(s->impl.view(), d_keys, d_off, stride, nullptr, n, np, W, d_owners, d_counts,
                                 rp::as_stream(stream));
     });
@@ -5493,7 +5518,7 @@ int rp_ring_moved_keys_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t
     return guard([&] {
         rp::Ring& r = R(h);
         const rp::Snap& s = S(before);
-        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "moved_keys_dev: null key buffer");
+        require_keys("moved_keys_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
         rp::moved_keys(r, s, d_keys, d_off, stride, nullptr, n, nrep, cap, d_idx, d_before, d_after, d_count,
                        rp::as_stream(stream));
@@ -5501,40 +5526,22 @@ int rp_ring_moved_keys_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t
 }
 
 // host-buffer forms: keys (or a caller hashFunc's key hashes) in, the moved list out
-static void host_moved(rp::Ring& r, const rp::Snap& s, const char* keys, const uint64_t* off, uint32_t stride,
-                       const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t cap, uint32_t* idx, uint32_t* brows,
-                       uint32_t* arows, uint32_t* count) {
+static void host_moved(rp::Ring& r, const rp::Snap& s, const KeySrc& k, uint64_t n, int32_t nrep, uint32_t cap,
+                       uint32_t* idx, uint32_t* brows, uint32_t* arows, uint32_t* count) {
     RP_REQUIRE(count, "moved_keys: null count");
     RP_REQUIRE(nrep <= 8, "moved_keys: nrep is at most 8 (the rows are compared in registers)");
     RP_REQUIRE(n < (1ull << 32), "moved_keys: at most 2^32-1 keys per call");
     RP_REQUIRE(cap == 0 || n == 0 || idx, "moved_keys: null index buffer");
     svc_stop(r);
-    const uint8_t* dk = nullptr;
-    const uint64_t* doff = nullptr;
-    const uint32_t* dh = nullptr;
-    if (n && hashes) {
-        r.io_a.reserve(n);
-        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
-        dh = r.io_a.p;
-    } else if (n) {
-        const uint64_t bytes = stride ? n * stride : off[n];
-        r.io_keys.reserve(bytes + 16);
-        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
-        dk = r.io_keys.p;
-        if (!stride) {
-            r.io_off.reserve(n + 1);
-            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-            doff = r.io_off.p;
-        }
-    }
+    const DevKeys d = stage_keys(r, k, n);
     // io_b = [count 1 | idx c | before rows c*W | after rows c*W], c = min(cap, n)
-    const uint64_t c = std::min<uint64_t>(cap, n), W = nrep > 1 ? (uint64_t)nrep : 1u;
+    const uint64_t c = std::min<uint64_t>(cap, n), W = rp::replicas(nrep, r.server_count).W;
     r.io_b.reserve(1 + c * (1 + 2 * W));
     uint32_t* dcount = r.io_b.p;
     uint32_t* didx = dcount + 1;
     uint32_t* dbr = didx + c;
     uint32_t* dar = dbr + c * W;
-    rp::moved_keys(r, s, dk, doff, stride, dh, n, nrep, (uint32_t)c, c ? didx : nullptr, brows ? dbr : nullptr,
+    rp::moved_keys(r, s, d.dk, d.doff, k.stride, d.dh, n, nrep, (uint32_t)c, c ? didx : nullptr, brows ? dbr : nullptr,
                    arows ? dar : nullptr, dcount, r.st);
     uint32_t total = 0;
     RP_HIP(hipMemcpyAsync(&total, dcount, 4, hipMemcpyDeviceToHost, r.st));
@@ -5556,8 +5563,9 @@ int rp_ring_moved_keys(rp_ring* h, const rp_ring_snap* before, const char* keys,
     return guard([&] {
         rp::Ring& r = R(h);
         const rp::Snap& s = S(before);
-        RP_REQUIRE(n == 0 || (keys && (stride || off)), "moved_keys: null key buffer");
-        host_moved(r, s, keys, off, stride, nullptr, n, nrep, cap, idx, before_rows, after_rows, count);
+        const KeySrc k = key_bytes(keys, off, stride);
+        require_keys("moved_keys", k, n);
+        host_moved(r, s, k, n, nrep, cap, idx, before_rows, after_rows, count);
     });
 }
 
@@ -5566,8 +5574,9 @@ int rp_ring_moved_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_t*
     return guard([&] {
         rp::Ring& r = R(h);
         const rp::Snap& s = S(before);
-        RP_REQUIRE(n == 0 || hashes, "moved_hashes: null hash buffer");
-        host_moved(r, s, nullptr, nullptr, 0, hashes, n, nrep, cap, idx, before_rows, after_rows, count);
+        const KeySrc k = key_hashes(hashes);
+        require_keys("moved_hashes", k, n);
+        host_moved(r, s, k, n, nrep, cap, idx, before_rows, after_rows, count);
     });
 }
 
@@ -5580,7 +5589,7 @@ int rp_ring_handoff_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t* d
     return guard([&] {
         rp::Ring& r = R(h);
         const rp::Snap& s = S(before);
-        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "handoff_dev: null key buffer");
+        require_keys("handoff_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
         rp::handoff(r, s, d_keys, d_off, stride, nullptr, n, nrep, only_src, cap, d_dests, d_group_off, d_key_idx,
                     d_src, d_slot, d_ndest, d_count, rp::as_stream(stream), false);
@@ -5588,11 +5597,10 @@ int rp_ring_handoff_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t* d
 }
 
 // host-buffer forms: keys (or a caller hashFunc's key hashes) in, the grouped plan out
-static void host_handoff(rp::Ring& r, const rp::Snap& s, const char* keys, const uint64_t* off, uint32_t stride,
-                         const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap,
-                         uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src, uint8_t* slot,
-                         uint32_t* ndest, uint32_t* count) {
-    const uint64_t W = nrep > 1 ? (uint64_t)nrep : 1u;
+static void host_handoff(rp::Ring& r, const rp::Snap& s, const KeySrc& k, uint64_t n, int32_t nrep, uint32_t only_src,
+                         uint32_t cap, uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src,
+                         uint8_t* slot, uint32_t* ndest, uint32_t* count) {
+    const uint64_t W = rp::replicas(nrep, r.server_count).W;
     RP_REQUIRE(ndest && count, "handoff: null count");
     RP_REQUIRE(nrep <= 8, "handoff: nrep is at most 8 (the rows are compared in registers)");
     RP_REQUIRE(n < (1ull << 32) && n * W < (1ull << 32), "handoff: n * max(nrep, 1) is at most 2^32-1 records");
@@ -5600,24 +5608,7 @@ static void host_handoff(rp::Ring& r, const rp::Snap& s, const char* keys, const
     RP_REQUIRE(only_src == rp::NIL || only_src < r.nt.size(), "handoff: only_src is not a server id of this ring");
     RP_REQUIRE(cap == 0 || n == 0 || (dests && goff && key_idx), "handoff: null output buffer");
     svc_stop(r);
-    const uint8_t* dk = nullptr;
-    const uint64_t* doff = nullptr;
-    const uint32_t* dh = nullptr;
-    if (n && hashes) {
-        r.io_a.reserve(n);
-        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
-        dh = r.io_a.p;
-    } else if (n) {
-        const uint64_t bytes = stride ? n * stride : off[n];
-        r.io_keys.reserve(bytes + 16);
-        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
-        dk = r.io_keys.p;
-        if (!stride) {
-            r.io_off.reserve(n + 1);
-            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-            doff = r.io_off.p;
-        }
-    }
+    const DevKeys d = stage_keys(r, k, n);
     // io = [count 1 | ndest 1 | group_off nd+1 | dests nd | key_idx c | src c | slot c bytes],
     // c = min(cap, n * W), nd = min(c, id bound)
     const uint64_t c = std::min<uint64_t>(cap, n * W), nd = std::min<uint64_t>(c, r.nt.size());
@@ -5629,8 +5620,8 @@ static void host_handoff(rp::Ring& r, const rp::Snap& s, const char* keys, const
     uint32_t* dki = dde + nd;
     uint32_t* dsr = dki + c;
     uint8_t* dsl = reinterpret_cast<uint8_t*>(dsr + c);
-    rp::handoff(r, s, dk, doff, stride, dh, n, nrep, only_src, (uint32_t)c, dde, dgo, dki, dsr, dsl, ws.io.p + 1,
-                ws.io.p, r.st, true);
+    rp::handoff(r, s, d.dk, d.doff, k.stride, d.dh, n, nrep, only_src, (uint32_t)c, dde, dgo, dki, dsr, dsl,
+                ws.io.p + 1, ws.io.p, r.st, true);
     uint32_t head[2] = {0, 0};
     RP_HIP(hipMemcpyAsync(head, ws.io.p, sizeof head, hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
@@ -5654,9 +5645,9 @@ int rp_ring_handoff(rp_ring* h, const rp_ring_snap* before, const char* keys, co
     return guard([&] {
         rp::Ring& r = R(h);
         const rp::Snap& s = S(before);
-        RP_REQUIRE(n == 0 || (keys && (stride || off)), "handoff: null key buffer");
-        host_handoff(r, s, keys, off, stride, nullptr, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot,
-                     ndest, count);
+        const KeySrc k = key_bytes(keys, off, stride);
+        require_keys("handoff", k, n);
+        host_handoff(r, s, k, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot, ndest, count);
     });
 }
 
@@ -5666,9 +5657,9 @@ int rp_ring_handoff_hashes(rp_ring* h, const rp_ring_snap* before, const uint32_
     return guard([&] {
         rp::Ring& r = R(h);
         const rp::Snap& s = S(before);
-        RP_REQUIRE(n == 0 || hashes, "handoff_hashes: null hash buffer");
-        host_handoff(r, s, nullptr, nullptr, 0, hashes, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot,
-                     ndest, count);
+        const KeySrc k = key_hashes(hashes);
+        require_keys("handoff_hashes", k, n);
+        host_handoff(r, s, k, n, nrep, only_src, cap, dests, group_off, key_idx, src, slot, ndest, count);
     });
 }
 
@@ -5703,24 +5694,7 @@ int rp_ring_route_views(rp_ring* h, const char* keys, const uint64_t* off, uint3
         RP_REQUIRE(n == 0 || hashes || stride || off, "route_views: null key offsets");
         RP_REQUIRE(V == 0 || rows, "route_views: null view rows");
         svc_stop(r);
-        const uint8_t* dk = nullptr;
-        const uint64_t* doff = nullptr;
-        const uint32_t* dh = nullptr;
-        if (n && hashes) {
-            r.io_a.reserve(n);
-            RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
-            dh = r.io_a.p;
-        } else if (n) {
-            const uint64_t bytes = stride ? n * stride : off[n];
-            r.io_keys.reserve(bytes + 16);
-            RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
-            dk = r.io_keys.p;
-            if (!stride) {
-                r.io_off.reserve(n + 1);
-                RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-                doff = r.io_off.p;
-            }
-        }
+        const DevKeys d = stage_keys(r, hashes ? key_hashes(hashes) : key_bytes(keys, off, stride), n);
         rp::RouteScratch& ws = r.route_ws;
         ws.use_on(r.st);
         // io8 = [rows V * row_stride | truth row_stride | active V]
@@ -5746,7 +5720,7 @@ int rp_ring_route_views(rp_ring* h, const char* keys, const uint64_t* off, uint3
             if (wrong) RP_HIP(hipMemcpyAsync(dwr, wrong, V * 8, hipMemcpyHostToDevice, r.st));
             if (lost) RP_HIP(hipMemcpyAsync(dlo, lost, V * 8, hipMemcpyHostToDevice, r.st));
         }
-        rp::route_views(r, dk, doff, stride, dh, n, drows, row_stride, bit, n_views, dcol, id_cap, dtruth, dact,
+        rp::route_views(r, d.dk, d.doff, stride, d.dh, n, drows, row_stride, bit, n_views, dcol, id_cap, dtruth, dact,
                         accumulate, reinterpret_cast<uint64_t*>(dwr), reinterpret_cast<uint64_t*>(dlo), dkw, dto, dow,
                         r.st);
         if (V) {
@@ -5776,7 +5750,7 @@ int rp_ring_owner_load_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_
                            int32_t nrep, uint32_t id_cap, int accumulate, uint64_t* d_load, void* stream) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "owner_load_dev: null key buffer");
+        require_keys("owner_load_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
         rp::owner_load(r, r.load_ws, d_keys, d_off, stride, nullptr, n, nrep, id_cap, accumulate,
                        reinterpret_cast<unsigned long long*>(d_load), rp::as_stream(stream));
@@ -5784,34 +5758,16 @@ int rp_ring_owner_load_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_
 }
 
 // host-buffer forms: keys (or a caller hashFunc's key hashes) in, the counters out
-static void host_owner_load(rp::Ring& r, const char* keys, const uint64_t* off, uint32_t stride,
-                            const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t id_cap, uint64_t* load) {
+static void host_owner_load(rp::Ring& r, const KeySrc& k, uint64_t n, int32_t nrep, uint32_t id_cap, uint64_t* load) {
     RP_REQUIRE(id_cap >= r.nt.size(), "owner_load: id_cap is below the ring's id bound (rp_ring_id_bound)");
     RP_REQUIRE(id_cap == 0 || load, "owner_load: null load buffer");
     svc_stop(r);
-    const uint64_t bins = (uint64_t)id_cap * (nrep > 1 ? (uint64_t)nrep : 1u);
+    const uint64_t bins = (uint64_t)id_cap * rp::replicas(nrep, r.server_count).W;
     if (bins == 0) return;
-    const uint8_t* dk = nullptr;
-    const uint64_t* doff = nullptr;
-    const uint32_t* dh = nullptr;
-    if (n && hashes) {
-        r.io_a.reserve(n);
-        RP_HIP(hipMemcpyAsync(r.io_a.p, hashes, n * 4, hipMemcpyHostToDevice, r.st));
-        dh = r.io_a.p;
-    } else if (n) {
-        const uint64_t bytes = stride ? n * stride : off[n];
-        r.io_keys.reserve(bytes + 16);
-        RP_HIP(hipMemcpyAsync(r.io_keys.p, keys, bytes, hipMemcpyHostToDevice, r.st));
-        dk = r.io_keys.p;
-        if (!stride) {
-            r.io_off.reserve(n + 1);
-            RP_HIP(hipMemcpyAsync(r.io_off.p, off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-            doff = r.io_off.p;
-        }
-    }
+    const DevKeys d = stage_keys(r, k, n);
     r.load_ws.use_on(r.st);
     r.load_ws.out.reserve(bins);
-    rp::owner_load(r, r.load_ws, dk, doff, stride, dh, n, nrep, id_cap, 0, r.load_ws.out.p, r.st);
+    rp::owner_load(r, r.load_ws, d.dk, d.doff, k.stride, d.dh, n, nrep, id_cap, 0, r.load_ws.out.p, r.st);
     RP_HIP(hipMemcpyAsync(load, r.load_ws.out.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
 }
@@ -5820,8 +5776,9 @@ int rp_ring_owner_load(rp_ring* h, const char* keys, const uint64_t* off, uint32
                        uint32_t id_cap, uint64_t* load) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || (keys && (stride || off)), "owner_load: null key buffer");
-        host_owner_load(r, keys, off, stride, nullptr, n, nrep, id_cap, load);
+        const KeySrc k = key_bytes(keys, off, stride);
+        require_keys("owner_load", k, n);
+        host_owner_load(r, k, n, nrep, id_cap, load);
     });
 }
 
@@ -5829,8 +5786,9 @@ int rp_ring_owner_load_hashes(rp_ring* h, const uint32_t* hashes, uint64_t n, in
                               uint64_t* load) {
     return guard([&] {
         rp::Ring& r = R(h);
-        RP_REQUIRE(n == 0 || hashes, "owner_load_hashes: null hash buffer");
-        host_owner_load(r, nullptr, nullptr, 0, hashes, n, nrep, id_cap, load);
+        const KeySrc k = key_hashes(hashes);
+        require_keys("owner_load_hashes", k, n);
+        host_owner_load(r, k, n, nrep, id_cap, load);
     });
 }
 
@@ -5839,18 +5797,17 @@ int rp_ring_snap_owner_load_dev(rp_ring_snap* s, const uint8_t* d_keys, const ui
                                 void* stream) {
     return guard([&] {
         RP_REQUIRE(s, "null snapshot handle");
-        RP_REQUIRE(n == 0 || (d_keys && (stride || d_off)), "snap_owner_load_dev: null key buffer");
+        require_keys("snap_owner_load_dev", key_bytes(d_keys, d_off, stride), n);
         rp::Snap& d = s->impl;
         RP_HIP(hipSetDevice(d.device));
-        const uint32_t W = nrep > 1 ? (uint32_t)nrep : 1u;
-        const int np = (int)std::min<int64_t>(nrep, d.server_count);  // lib/ring/index.js:159-162
+        const rp::Replicas rep = rp::replicas(nrep, d.server_count);
         hipStream_t st = rp::as_stream(stream);
         rp::owner_load_walk(d.load_ws, n, nrep, d.id_bound, id_cap, d.M != 0, accumulate,
                             reinterpret_cast<unsigned long long*>(d_load), d.device, st,
                             [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
                                 rp::launch_lookupn_view(d.view(), stride ? d_keys + k0 * stride : d_keys,
-                                                        stride ? nullptr : d_off + k0, stride, nullptr, cnt, np, W, rows,
-                                                        nullptr, st);
+                                                        stride ? nullptr : d_off + k0, stride, nullptr, cnt, rep.np, rep.W,
+                                                        rows, nullptr, st);
                             });
     });
 }
