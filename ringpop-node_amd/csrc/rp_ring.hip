@@ -725,7 +725,7 @@ __device__ __forceinline__ void lookupn_redo(const uint8_t* __restrict__ keys, c
 // Phase cycle counters of the lean kernel (diagnostics only: built with -DRP_LK_PROF by
 // tools/build_prof.sh; the product build has none of this). A wave stamps s_memtime at each
 // phase boundary, the stamp depending on the phase's last result; the per-phase sums over all
-// waves land in g_lk_prof (printed by launch_lookupn under RP_LK_PROF_PRINT).
+// waves land in g_lk_prof (printed by lookupn_compact under RP_LK_PROF_PRINT).
 #ifdef RP_LK_PROF
 __device__ unsigned long long g_lk_prof[10];
 #define LK_T(var, dep) \
@@ -2682,6 +2682,108 @@ struct RouteScratch {
     void use_on(hipStream_t st) { order.use_on(st); }
 };
 
+// Every environment variable of the batch-lookup launch path (A/B and diagnostics; none is API).
+// lookup_knobs() reads them at every call and nothing keeps them: the tests and tools/ab_*.py
+// change them between calls of one process. Which kernel a value selects: launch_lookupn below.
+struct LookupKnobs {
+    // RP_RING_WIDE: neither the compact nor the packed layout, the wide binary-search kernels
+    bool wide;
+    // RP_RING_LAYOUT=packed: not the compact layout, the packed probe kernel
+    bool layout_packed;
+    // RP_RING_NOWINDOW: the packed layout through the generic kernels, not the window probe
+    bool nowindow;
+    // RP_LOOKUP_ABLATE: timing ablations (results wrong) of the fixed, probe and compact kernels
+    bool ablate_set;  // set at all, "0" too: the LDS-index kernel stays off (tools/ab_cb.py)
+    int ablate;       // its number: CompactView::ablate, the fixed and probe kernels' MODE
+    // RP_LOOKUP_WPRED=0: window 1 at the bucket start, not the predicted start
+    bool wpred;
+    // RP_LOOKUP_HINT=0: lookupN(3) without the hinted index
+    bool hint;
+    // RP_LOOKUP_LDS=1: the LDS-index kernel; any other value keeps it off (unset: kLdsDefault)
+    bool lds;
+    // RP_LOOKUP_LDS_GRID: its workgroups (0: unset, one a CU)
+    uint64_t lds_grid;
+    // RP_LOOKUP_LDS_STG=1: its keys through coalesced loads transposed in LDS
+    bool lds_stg;
+    // RP_LOOKUP_LDS_ABL: its timing ablations for lookupN(3) (results wrong)
+    int lds_abl;
+    // RP_LOOKUP_WS="NP:NC": the wave-specialised kernel with NP producer and NC consumer waves
+    bool ws;             // set and not "0"
+    int ws_np, ws_nc;    // "1" or any text without ':' means 1:3; a malformed pair gives ws_np = 0
+    // RP_LOOKUP_WS_GRID: its workgroups (0: unset, what fits the CUs)
+    uint64_t ws_grid;
+    // RP_LOOKUP_WS_ABL: timing ablations of its 4:12 shape (results wrong)
+    int ws_abl;
+    // RP_LOOKUP_KPL: keys per lane of the compact, lean and probe kernels
+    bool kpl_set;  // set, whatever the value: no sorted and no wave-specialised kernel
+    int kpl;       // its number; each path maps it to the tiles it has
+    // RP_LOOKUP_SORT: threads of the sorted-tile kernel, 0 = off (unset: kSortDefault)
+    int sort_t;
+    // RP_LOOKUP_GRID: workgroups of the sorted, lean and compact kernels (0: unset)
+    uint64_t grid;
+    // RP_LOOKUP_LEAN=0: the round-1 compact kernel, not the lean one
+    bool lean_set;  // set, whatever the value: no sorted kernel
+    bool lean;
+    // RP_LOOKUP_HALF: LDS slices of the lean kernel's key stage (2, 4)
+    bool half_set;  // set, whatever the value: no sorted kernel
+    int half;
+    // RP_LOOKUP_FUSEFIX: deferred keys finished by the lean kernel's own workgroups; no sorted kernel
+    bool fusefix;
+    // RP_LOOKUP_STG: the lean kernel's key slices by DMA (1: compiler-issued, 2: from asm)
+    bool stg_set;  // set, whatever the value: no sorted kernel
+    int stg;
+    // RP_LOOKUP_LH: the lean kernel's lookups in 1 or 2 halves (0: unset or not positive)
+    bool lh_set;  // set, whatever the value: no sorted kernel
+    uint64_t lh;
+    // RP_LOOKUP_STGHS: key slices of RP_LOOKUP_STG=2 (4, 8)
+    uint64_t stghs;
+    // RP_LOOKUP_DEBUG: a census of the deferred keys on stderr after every tiled launch
+    bool debug;
+    // RP_LK_PROF_PRINT: the phase cycle counters of a -DRP_LK_PROF build on stderr
+    bool prof_print;
+};
+static LookupKnobs lookup_knobs() {
+    const auto num = [](const char* v) { return v ? atoi(v) : 0; };
+    const auto is0 = [](const char* v) { return v && !strcmp(v, "0"); };
+    const char *lay = getenv("RP_RING_LAYOUT"), *abl = getenv("RP_LOOKUP_ABLATE"), *lds = getenv("RP_LOOKUP_LDS"),
+               *ws = getenv("RP_LOOKUP_WS"), *kpl = getenv("RP_LOOKUP_KPL"), *sort = getenv("RP_LOOKUP_SORT"),
+               *lean = getenv("RP_LOOKUP_LEAN"), *half = getenv("RP_LOOKUP_HALF"), *stg = getenv("RP_LOOKUP_STG");
+    LookupKnobs k;
+    k.wide = getenv_flag("RP_RING_WIDE");
+    k.layout_packed = lay && !strcmp(lay, "packed");
+    k.nowindow = getenv_flag("RP_RING_NOWINDOW");
+    k.ablate_set = abl != nullptr;
+    k.ablate = num(abl);
+    k.wpred = !is0(getenv("RP_LOOKUP_WPRED"));
+    k.hint = !is0(getenv("RP_LOOKUP_HINT"));
+    k.lds = lds ? !strcmp(lds, "1") : kLdsDefault;
+    k.lds_grid = env_pos("RP_LOOKUP_LDS_GRID", 0);
+    k.lds_stg = (int)env_pos("RP_LOOKUP_LDS_STG", 0) == 1;
+    k.lds_abl = num(getenv("RP_LOOKUP_LDS_ABL"));
+    k.ws = ws && !is0(ws);
+    k.ws_np = 1, k.ws_nc = 3;
+    if (k.ws && strchr(ws, ':') && sscanf(ws, "%d:%d", &k.ws_np, &k.ws_nc) != 2) k.ws_np = 0;
+    k.ws_grid = env_pos("RP_LOOKUP_WS_GRID", 0);
+    k.ws_abl = num(getenv("RP_LOOKUP_WS_ABL"));
+    k.kpl_set = kpl != nullptr;
+    k.kpl = num(kpl);
+    k.sort_t = sort ? atoi(sort) : kSortDefault;
+    k.grid = env_pos("RP_LOOKUP_GRID", 0);
+    k.lean_set = lean != nullptr;
+    k.lean = !is0(lean);
+    k.half_set = half != nullptr;
+    k.half = num(half);
+    k.fusefix = getenv_flag("RP_LOOKUP_FUSEFIX");
+    k.stg_set = stg != nullptr;
+    k.stg = num(stg);
+    k.lh_set = getenv("RP_LOOKUP_LH") != nullptr;
+    k.lh = env_pos("RP_LOOKUP_LH", 0);
+    k.stghs = env_pos("RP_LOOKUP_STGHS", 8);
+    k.debug = getenv_flag("RP_LOOKUP_DEBUG");
+    k.prof_print = getenv_flag("RP_LK_PROF_PRINT");
+    return k;
+}
+
 struct Ring {
     int device = 0;
     hipStream_t st = nullptr;
@@ -2757,13 +2859,10 @@ struct Ring {
         return RingView{tok.p, own.p, bstart.p, M, 32u - bbits};
     }
     PackedView pview() const { return PackedView{ent.p, pbstart.p, M, pbits}; }
-    CompactView cview() const {
-        const char* a = getenv("RP_LOOKUP_ABLATE");
-        return CompactView{cent.p, cidx.p, M, ccb, cob, cfsh, cfsh == 0, a ? (uint32_t)atoi(a) : 0u,
+    CompactView cview(const LookupKnobs& k) const {
+        return CompactView{cent.p, cidx.p, M, ccb, cob, cfsh, cfsh == 0, (uint32_t)k.ablate,
                            (uint32_t)(3ull * ((uint64_t)M + kEnt3Pad + 6) + 16), (uint32_t)(8ull << (ccb - 3)),
-                           getenv("RP_LOOKUP_WPRED") && !strcmp(getenv("RP_LOOKUP_WPRED"), "0") ? 0u : 1u,
-                           chint && !(getenv("RP_LOOKUP_HINT") && !strcmp(getenv("RP_LOOKUP_HINT"), "0")) ? cidxh.p
-                                                                                                       : nullptr};
+                           k.wpred ? 1u : 0u, chint && k.hint ? cidxh.p : nullptr};
     }
 };
 
@@ -3003,46 +3102,352 @@ static void ring_compute_checksum(Ring& r) {
     r.has_checksum = true;
 }
 
+// ------------------------------------------------------------------- batch lookup launch
+// launch_lookupn (below) tries, in this order: the LDS-index kernel, the wave-specialised kernel,
+// the compact layout's sorted / lean / round-1 kernels, the packed window probe, and then the
+// generic kernels over the packed or the wide view.
+
+// Compute units of `device` (256 when the query fails). Every caller passes its handle's device,
+// which the C ABI made the current one.
+static int cu_count(int device) {
+    int c = 0;
+    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device);
+    return c > 0 ? c : 256;
+}
+
+// f(Int<N>{}) for the N = 1..4 owners a row the tiled kernels are built for
+template <int N>
+using Int = std::integral_constant<int, N>;
+template <class F>
+static void with_need(int need, F&& f) {
+    switch (need) {
+        case 1: f(Int<1>{}); break;
+        case 2: f(Int<2>{}); break;
+        case 3: f(Int<3>{}); break;
+        default: f(Int<4>{}); break;
+    }
+}
+
+// The kernels over any view: 36-byte keys at a 4-byte-aligned address in registers
+// (k_lookupn_fixed), every other key form and caller hashes per thread (k_lookupn_generic).
+// `ablate`: LookupKnobs::ablate.
 template <class View>
 static void launch_lookupn_view(const View& rv, const uint8_t* keys, const uint64_t* off, uint32_t stride,
                                 const uint32_t* hashes, uint64_t n, int np, uint32_t W, uint32_t* out,
-                                uint8_t* counts, hipStream_t st) {
-    const unsigned grid_fixed = grid_for(n, kLkThreads, 256 * 8);
+                                uint8_t* counts, hipStream_t st, int ablate) {
     const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const int need = np <= 0 ? 1 : np;
-    const int ablate = getenv("RP_LOOKUP_ABLATE") ? atoi(getenv("RP_LOOKUP_ABLATE")) : 0;
-    if (fixed36 && W <= 4 && need <= 4 && need > 1 && ablate == 1) {
-        hipLaunchKernelGGL((k_lookupn_fixed<36, 4, View, 1>), dim3(grid_fixed), dim3(kLkThreads), 0, st, keys, n, rv,
+    const auto fixed = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid_for(n, kLkThreads, 256 * 8)), dim3(kLkThreads), 0, st, keys, n, rv, np, W,
+                           out, counts);
+    };
+    const auto generic = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(grid_for(n, 256, 256 * 8)), dim3(256), 0, st, keys, off, stride, hashes, n, rv,
                            np, W, out, counts);
-    } else if (fixed36 && W <= 4 && need <= 4 && need > 1 && ablate == 2) {
-        hipLaunchKernelGGL((k_lookupn_fixed<36, 4, View, 2>), dim3(grid_fixed), dim3(kLkThreads), 0, st, keys, n, rv,
-                           np, W, out, counts);
-    } else if (fixed36 && W <= 8 && need <= 8) {
-        if (need == 1 && W == 1)
-            hipLaunchKernelGGL((k_lookupn_fixed<36, 1, View>), dim3(grid_fixed), dim3(kLkThreads), 0, st, keys, n,
-                               rv, np, W, out, counts);
-        else if (need <= 4 && W <= 4)
-            hipLaunchKernelGGL((k_lookupn_fixed<36, 4, View>), dim3(grid_fixed), dim3(kLkThreads), 0, st, keys, n,
-                               rv, np, W, out, counts);
-        else
-            hipLaunchKernelGGL((k_lookupn_fixed<36, 8, View>), dim3(grid_fixed), dim3(kLkThreads), 0, st, keys, n,
-                               rv, np, W, out, counts);
-    } else {
-        const unsigned g = grid_for(n, 256, 256 * 8);
-        if (need == 1)
-            hipLaunchKernelGGL((k_lookupn_generic<1, View>), dim3(g), dim3(256), 0, st, keys, off, stride, hashes,
-                               n, rv, np, W, out, counts);
-        else if (need <= 4)
-            hipLaunchKernelGGL((k_lookupn_generic<4, View>), dim3(g), dim3(256), 0, st, keys, off, stride, hashes,
-                               n, rv, np, W, out, counts);
-        else if (need <= 8)
-            hipLaunchKernelGGL((k_lookupn_generic<8, View>), dim3(g), dim3(256), 0, st, keys, off, stride, hashes,
-                               n, rv, np, W, out, counts);
-        else
-            hipLaunchKernelGGL((k_lookupn_generic<0, View>), dim3(g), dim3(256), 0, st, keys, off, stride, hashes,
-                               n, rv, np, W, out, counts);
+    };
+    if (fixed36 && W <= 4 && need <= 4 && need > 1 && ablate == 1)
+        fixed(k_lookupn_fixed<36, 4, View, 1>);
+    else if (fixed36 && W <= 4 && need <= 4 && need > 1 && ablate == 2)
+        fixed(k_lookupn_fixed<36, 4, View, 2>);
+    else if (fixed36 && need == 1 && W == 1)
+        fixed(k_lookupn_fixed<36, 1, View>);
+    else if (fixed36 && need <= 4 && W <= 4)
+        fixed(k_lookupn_fixed<36, 4, View>);
+    else if (fixed36 && need <= 8 && W <= 8)
+        fixed(k_lookupn_fixed<36, 8, View>);
+    else if (need == 1)
+        generic(k_lookupn_generic<1, View>);
+    else if (need <= 4)
+        generic(k_lookupn_generic<4, View>);
+    else if (need <= 8)
+        generic(k_lookupn_generic<8, View>);
+    else
+        generic(k_lookupn_generic<0, View>);
+    RP_HIP(hipGetLastError());
+}
+
+// A batch of 36-byte keys at a 4-byte-aligned address: what the tiled and the probe kernels take.
+struct Batch36 {
+    const uint8_t* keys;
+    uint64_t n;
+    int np, need;  // need = max(np, 1)
+    uint32_t W;
+    uint32_t* out;
+    uint8_t* counts;
+    hipStream_t st;
+};
+
+// The end of every tiled path. The tile kernels left the keys they could not finish in `nlists`
+// lists, one per TK-key tile from the first key on: finish those exactly (`fix`; the compact path
+// turns it off), print their census under RP_LOOKUP_DEBUG through line(keys done, deferred,
+// overflowed lists, the nlists + extra words of r.nslow), and send the keys past `done`, the
+// partial last tile, through the wide view.
+template <class Line>
+static void lookupn_tiles_end(Ring& r, const LookupKnobs& k, const Batch36& b, uint64_t nlists, uint64_t TK,
+                              uint64_t done, bool fix, uint64_t extra, Line&& line) {
+    if (fix) {
+        const CompactFixView fv{r.tok.p, r.own.p, r.cidx.p, r.view(), r.M, r.ccb};
+        const uint64_t fthreads = nlists * kSlowPerTile;
+        hipLaunchKernelGGL((k_lookupn_fix_tiles<CompactFixView>), dim3((unsigned)((fthreads + 255) / 256)), dim3(256),
+                           0, b.st, b.keys, fv, b.np, b.W, b.out, b.counts, r.slow.p, r.nslow.p, nlists, (uint32_t)TK);
     }
     RP_HIP(hipGetLastError());
+    if (k.debug) {
+        std::vector<uint32_t> c(nlists + extra);
+        RP_HIP(hipMemcpyAsync(c.data(), r.nslow.p, 4 * (nlists + extra), hipMemcpyDeviceToHost, b.st));
+        RP_HIP(hipStreamSynchronize(b.st));
+        uint64_t tot = 0, over = 0;
+        for (uint64_t t = 0; t < nlists; t++) {
+            tot += c[t];
+            over += c[t] > kSlowPerTile;
+        }
+        line((unsigned long long)done, (unsigned long long)tot, (unsigned long long)over, c.data());
+    }
+    if (done < b.n)
+        launch_lookupn_view(r.view(), b.keys + done * 36, nullptr, 36, nullptr, b.n - done, b.np, b.W,
+                            b.out + done * b.W, b.counts ? b.counts + done : nullptr, b.st, k.ablate);
+}
+
+// The LDS-index kernel (round 6; RP_LOOKUP_LDS=0 keeps the lean kernel, 1 forces this one)
+static bool lookupn_lds(Ring& r, const LookupKnobs& k, const Batch36& b) {
+    if (!k.lds || b.n < 64ull * 8 || k.ablate_set) return false;
+    if (r.lds_pending) ring_build_lds(r);
+    if (!r.lds) return false;
+    RP_REQUIRE(b.n < (1ull << 32), "lookupn: at most 2^32-1 keys per call");
+    constexpr int KPL = 8;
+    const uint64_t TK = 64ull * KPL, nwt = b.n / TK;
+    r.slow.reserve(nwt * kSlowPerTile + 1);
+    r.nslow.reserve(nwt + 1);
+    const unsigned g = (unsigned)std::min<uint64_t>(k.lds_grid ? k.lds_grid : (uint64_t)cu_count(r.device),
+                                                    (nwt + kLdsThreads / 64 - 1) / (kLdsThreads / 64));
+    const LdsView lv{r.lent.p, r.lidx.p, r.M, r.lng, r.llg, r.lfb, r.cob,
+                     (uint32_t)(3ull * ((uint64_t)r.M + kEnt3Pad + 6) + 16)};
+    const auto tiles = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(g), dim3(kLdsThreads), 0, b.st, b.keys, nwt, lv, b.out, b.counts, r.slow.p,
+                           r.nslow.p);
+    };
+    if (b.need == 3 && k.lds_abl) {  // diagnostics: time ablations (results wrong)
+        switch (k.lds_abl) {
+            case 1: tiles(k_lookupn_lds<KPL, 3, 0, 1>); break;
+            case 2: tiles(k_lookupn_lds<KPL, 3, 0, 2>); break;
+            case 3: tiles(k_lookupn_lds<KPL, 3, 0, 3>); break;
+            case 4: tiles(k_lookupn_lds<KPL, 3, 0, 4>); break;
+            default: tiles(k_lookupn_lds<KPL, 3, 0, 7>); break;
+        }
+    } else {
+        with_need(b.need, [&](auto need) {
+            constexpr int N = decltype(need)::value;
+            if (k.lds_stg)
+                tiles(k_lookupn_lds<KPL, N, 1, 0>);
+            else
+                tiles(k_lookupn_lds<KPL, N, 0, 0>);
+        });
+    }
+    RP_HIP(hipGetLastError());
+    lookupn_tiles_end(r, k, b, nwt, TK, nwt * TK, true, 0,
+                      [&](auto done, auto tot, auto over, const uint32_t*) {
+                          fprintf(stderr, "[rp] lds lookupN: %llu keys, %llu deferred, %llu overflowed tiles (ng %u fb %u ob %u)\n",
+                                  done, tot, over, r.lng, r.lfb, r.cob);
+                      });
+    return true;
+}
+
+// The wave-specialised kernel (round 6, A/B): RP_LOOKUP_WS = "NP:NC" producer and consumer
+// waves a workgroup (1:3, 2:6, 1:7, 4:12, 2:2, 1:15, 2:14; "1" = 1:3)
+static bool lookupn_ws(Ring& r, const LookupKnobs& k, const Batch36& b, const CompactView& cv) {
+    const uint64_t n = b.n;
+    if (!k.ws || b.need != 3 || k.kpl_set || cv.ablate != 0 || n < 512ull * 4 || n * 12ull >= (1ull << 31))
+        return false;
+    const int wnp = k.ws_np, wnc = k.ws_nc;
+    constexpr uint64_t TK = 512;
+    const uint64_t nwt = n / TK;
+    r.slow.reserve(nwt * kSlowPerTile + 1);
+    r.nslow.reserve(nwt + 2);
+    uint32_t* err = r.nslow.p + nwt + 1;
+    RP_HIP(hipMemsetAsync(err, 0, 4, b.st));
+    const uint64_t nwg = (nwt + (uint64_t)wnc - 1) / (uint64_t)(wnc > 0 ? wnc : 1);
+    // workgroups a CU: 16 waves (<= 128 VGPRs), and the LDS (an 18-KB key tile a producer,
+    // kWsSlots 2-KB ring slots and a 768-B list a consumer)
+    const uint64_t lds_wg = (uint64_t)wnp * 18432 + (uint64_t)wnc * (kWsSlots * 2048 + 780);
+    const uint64_t per_cu = wnp + wnc > 0 ? std::max<uint64_t>(1, std::min<uint64_t>(16 / (uint64_t)(wnp + wnc), 163840 / lds_wg)) : 1;
+    const unsigned g = (unsigned)std::min<uint64_t>(nwg, k.ws_grid ? k.ws_grid : (uint64_t)cu_count(r.device) * per_cu);
+    // the shapes built; RP_LOOKUP_WS_ABL = 1 | 2 (diagnostics) takes an ablated 4:12
+    using Kernel = decltype(&k_lookupn_ws<1, 3>);
+    static const struct { int np, nc, abl; Kernel kern; } shapes[] = {
+        {1, 3, 0, k_lookupn_ws<1, 3>},      {2, 6, 0, k_lookupn_ws<2, 6>},      {1, 7, 0, k_lookupn_ws<1, 7>},
+        {4, 12, 1, k_lookupn_ws<4, 12, 1>}, {4, 12, 2, k_lookupn_ws<4, 12, 2>}, {4, 12, 0, k_lookupn_ws<4, 12>},
+        {2, 2, 0, k_lookupn_ws<2, 2>},      {1, 15, 0, k_lookupn_ws<1, 15>},    {2, 14, 0, k_lookupn_ws<2, 14>}};
+    Kernel kern = nullptr;
+    for (const auto& s : shapes)
+        if (!kern && s.np == wnp && s.nc == wnc && (s.abl == 0 || s.abl == k.ws_abl)) kern = s.kern;
+    RP_REQUIRE(kern, "RP_LOOKUP_WS: one of 1:3, 2:6, 1:7, 4:12, 2:2, 1:15, 2:14");
+    hipLaunchKernelGGL(kern, dim3(g), dim3((wnp + wnc) * 64), 0, b.st, b.keys, nwt, cv, b.out, (uint32_t)(n * 12ull), b.counts,
+                       r.slow.p, r.nslow.p, err);
+    RP_HIP(hipGetLastError());
+    lookupn_tiles_end(r, k, b, nwt, TK, nwt * TK, true, 2,
+                      [&](auto done, auto tot, auto over, const uint32_t* c) {
+                          fprintf(stderr, "[rp] ws lookupN %d:%d: %llu keys, %llu deferred, %llu overflowed wave-tiles, err %u\n", wnp,
+                                  wnc, done, tot, over, c[nwt + 1]);
+                      });
+    return true;
+}
+
+// The compact layout's own kernels: whole sorted tiles first (lookupN(3) only), whole tiles of
+// the lean kernel (RP_LOOKUP_LEAN=0: the round-1 kernel) after them.
+static void lookupn_compact(Ring& r, const LookupKnobs& k, const Batch36& b, const CompactView& cv) {
+    const uint64_t n = b.n;
+    const int need = b.need, np = b.np;
+    const hipStream_t st = b.st;
+    // lookupN(3) (the C2 bench): 8 keys per lane, staged through LDS in four slices (0.925-0.926
+    // against 0.962-0.970 ms for 4 keys per lane; two slices 0.926-0.932; 6 keys per lane
+    // 0.956-0.959; profiles/r02/ab_lookup_lean.json); the other widths 4 keys per lane.
+    // RP_LOOKUP_KPL / RP_LOOKUP_HALF (slices: 2, 4) override (A/B).
+    int kpl = k.kpl_set ? k.kpl : (need == 3 ? 8 : 4);
+    if (kpl != 1 && kpl != 2 && !((kpl == 3 || kpl == 8) && need == 3)) kpl = 4;  // the instantiated tiles
+    // The sorted-tile kernel (RP_LOOKUP_SORT = 256 (default) | 512 | 1024 threads, 0 = off): only where
+    // the lean <8, 3, 4> kernel runs by default (lookupN(3) over the hinted index, no other
+    // RP_LOOKUP_* shape knob). It takes the whole tiles of 8 x threads keys; the rest goes on
+    // to the lean kernel's 2,048-key tiles and the generic kernel as before, and one fix pass
+    // covers both (the sorted kernel defers into the same 2,048-key lists).
+    int sort_t = k.sort_t;
+    RP_REQUIRE(sort_t == 0 || sort_t == 256 || sort_t == 512 || sort_t == 1024, "RP_LOOKUP_SORT: one of 0, 256, 512, 1024");
+    if (need != 3 || !cv.idxh || cv.ablate != 0 || n < 8ull * (uint64_t)sort_t || k.kpl_set || k.half_set ||
+        k.lean_set || k.stg_set || k.lh_set || k.fusefix)
+        sort_t = 0;
+    const uint64_t stiles = sort_t ? n / (8ull * (uint64_t)sort_t) : 0;
+    const uint64_t s0 = stiles * 8ull * (uint64_t)sort_t;  // keys the sorted kernel takes
+    const uint64_t t0 = s0 / 2048;                         // their 2,048-key lists
+    if (!sort_t && n < (uint64_t)kLkThreads * kpl) kpl = 4;  // at least one whole tile
+    const uint64_t TK = (uint64_t)kLkThreads * kpl;
+    const uint64_t ntiles = (n - s0) / TK, done = s0 + ntiles * TK;
+    r.slow.reserve((t0 + ntiles) * kSlowPerTile + 1);
+    r.nslow.reserve(t0 + ntiles + 1);
+    if (stiles) {
+        // workgroups, tiles strided over them (2^26 C2 keys, profiles/sorted_tiles/grid_sweep.txt):
+        // 256 threads 0.842 ms at 4096 (2048: 0.877, 8192: 0.845, 12288: 0.850); 512 threads 0.890
+        // at 8192 (1024-4096: 0.93-0.95); 1024 threads 0.997 at 512-1024. RP_LOOKUP_GRID overrides (A/B).
+        const unsigned sg = grid_for(stiles, 1, (unsigned)(k.grid ? k.grid : sort_t == 256 ? 4096u : sort_t == 512 ? 8192u : 1024u));
+        const auto sorted = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(sg), dim3(sort_t), 0, st, b.keys, stiles, cv, b.out, b.counts, r.slow.p, r.nslow.p);
+        };
+        if (sort_t == 256)
+            sorted(k_lookupn_sorted<256, 3>);
+        else if (sort_t == 512)
+            sorted(k_lookupn_sorted<512, 3>);
+        else
+            sorted(k_lookupn_sorted<1024, 3>);
+        RP_HIP(hipGetLastError());
+    }
+    const bool lean = k.lean;  // A/B: RP_LOOKUP_LEAN=0 = round-1 kernel
+    // workgroups, tiles strided over them: the lean kernel at 4096 (4 rounds of the 1024 that
+    // fit, 8 tiles each at C2) ran 0.905-0.911 ms against 0.926-0.930 at 2048 (3072: 0.917;
+    // 5120-16384: 0.908-0.914; profiles/r02/ab_lookup_grid.json). RP_LOOKUP_GRID overrides (A/B).
+    const unsigned g = grid_for(ntiles, 1, (unsigned)(k.grid ? k.grid : lean ? 4096u : 2048u));
+    const int half = k.half_set ? k.half : (kpl == 8 ? 4 : 0);
+    const CompactFixView fv{r.tok.p, r.own.p, r.cidx.p, r.view(), r.M, r.ccb};
+    // deferred keys finished by the lean kernel's own workgroups (A/B): only <8, 3, 4>
+    const bool fuse = k.fusefix && lean && half == 4 && kpl == 8 && need == 3 && cv.ablate != 3;
+    const bool stg1 = k.stg == 1 && lean && half == 4 && kpl == 8 && need == 3 && !fuse;
+    // RP_LOOKUP_STG=2: asm DMA ring (RP_LOOKUP_STGHS = 4 | 8 key slices; RP_LOOKUP_LH = 1 | 2)
+    const bool stg2 = lean && kpl == 8 && need == 3 && !fuse && k.stg == 2;
+    const int lh = (lean && (half == 4 || stg2) && kpl == 8 && need == 3 && !fuse)
+                       ? (int)(k.lh ? k.lh : (stg2 ? 2u : 1u)) : 1;
+    const int stghs = (int)k.stghs;
+    // the lean kernel's share: the keys after the sorted tiles, and their lists
+    const auto tiles = [&](auto kern, auto... fix) {
+        hipLaunchKernelGGL(kern, dim3(g), dim3(kLkThreads), 0, st, b.keys + s0 * 36, ntiles, cv, b.out + s0 * b.W,
+                           b.counts ? b.counts + s0 : nullptr, r.slow.p + t0 * kSlowPerTile, r.nslow.p + t0, fix...);
+    };
+    const auto run = [&](auto keys_per_lane, auto owners) {
+        constexpr int KPL = decltype(keys_per_lane)::value, NEED = decltype(owners)::value;
+        if (!lean) return tiles(k_lookupn_compact<KPL, NEED>);
+        if constexpr (KPL == 8 && NEED == 3) {  // the staging variants exist for this tile only
+            if (stg2 && stghs == 8 && lh == 1) return tiles(k_lookupn_lean<8, 3, 8, false, 2, 1>, fv, np);
+            if (stg2 && stghs == 8) return tiles(k_lookupn_lean<8, 3, 8, false, 2, 2>, fv, np);
+            if (stg2) return tiles(k_lookupn_lean<8, 3, 4, false, 2, 2>, fv, np);
+            if (stg1 && lh == 2) return tiles(k_lookupn_lean<8, 3, 4, false, 1, 2>, fv, np);
+            if (lh == 2) return tiles(k_lookupn_lean<8, 3, 4, false, 0, 2>, fv, np);
+            if (stg1) return tiles(k_lookupn_lean<8, 3, 4, false, 1>, fv, np);
+        }
+        if (half == 4 && KPL % 4 == 0 && fuse) return tiles(k_lookupn_lean<KPL, NEED, (KPL % 4 == 0 ? 4 : 1), true>, fv, np);
+        if (half == 4 && KPL % 4 == 0) return tiles(k_lookupn_lean<KPL, NEED, (KPL % 4 == 0 ? 4 : 1)>, fv, np);
+        if (half == 2 && KPL % 2 == 0) return tiles(k_lookupn_lean<KPL, NEED, (KPL % 2 == 0 ? 2 : 1)>, fv, np);
+        return tiles(k_lookupn_lean<KPL, NEED>, fv, np);
+    };
+    if (ntiles == 0) {  // the sorted kernel took every whole tile
+    } else if (kpl == 1) {
+        with_need(need, [&](auto owners) { run(Int<1>{}, owners); });
+    } else if (kpl == 2) {
+        with_need(need, [&](auto owners) { run(Int<2>{}, owners); });
+    } else if (kpl == 8 && need == 3) {
+        run(Int<8>{}, Int<3>{});
+    } else if (kpl == 3 && need == 3) {
+        run(Int<3>{}, Int<3>{});
+    } else {
+        with_need(need, [&](auto owners) { run(Int<4>{}, owners); });
+    }
+#ifdef RP_LK_PROF
+    if (k.prof_print) {
+        unsigned long long v[10];
+        RP_HIP(hipStreamSynchronize(st));
+        RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_lk_prof), sizeof v));
+        const double nw = (double)(v[6] ? v[6] : 1);
+        fprintf(stderr,
+                "[rp] lean phase cycles per wave-tile (%llu): keys-arrive %.0f hash-all %.0f idx %.0f win1+loop %.0f "
+                "finish2 %.0f barrier+store %.0f\n",
+                v[6], v[0] / nw, v[1] / nw, v[2] / nw, v[3] / nw, v[4] / nw, v[5] / nw);
+        memset(v, 0, sizeof v);
+        RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_lk_prof), v, sizeof v));
+        if (stiles) {
+            RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_sk_prof), sizeof v));
+            const double sw = (double)(v[6] ? v[6] : 1);
+            fprintf(stderr,
+                    "[rp] sorted<%d> phase cycles per wave-tile (%llu): keys+hash %.0f sort+deal %.0f idx+win-issue %.0f "
+                    "win1+loop %.0f finish2 %.0f barrier+store %.0f\n",
+                    sort_t, v[6], v[0] / sw, v[1] / sw, v[2] / sw, v[3] / sw, v[4] / sw, v[5] / sw);
+            memset(v, 0, sizeof v);
+            RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_sk_prof), v, sizeof v));
+        }
+    }
+#endif
+    // (t0 > 0: TK is 2048, the lists are uniform)
+    lookupn_tiles_end(r, k, b, t0 + ntiles, TK, done, cv.ablate != 3 && !fuse, 0,
+                      [&](auto keys_done, auto tot, auto over, const uint32_t*) {
+                          fprintf(stderr, "[rp] compact lookupN: %llu keys, %llu deferred, %llu overflowed tiles (cb %u ob %u fsh %u sort %d)\n",
+                                  keys_done, tot, over, r.ccb, r.cob, r.cfsh, sort_t);
+                      });
+}
+
+// The packed layout's window probe, its deferred keys finished by k_lookupn_fix
+static bool lookupn_probe(Ring& r, const LookupKnobs& k, const Batch36& b) {
+    if (b.W > 4 || b.need > 4 || k.nowindow) return false;
+    RP_REQUIRE(b.n < (1ull << 32), "lookupn: at most 2^32-1 keys per call");
+    r.slow.reserve(b.n + 1);
+    r.nslow.reserve(1);
+    RP_HIP(hipMemsetAsync(r.nslow.p, 0, sizeof(uint32_t), b.st));
+    const int kpl = k.kpl_set ? k.kpl : kDefaultKPL;
+    const PackedView pv = r.pview();
+    const auto probe = [&](auto keys_per_lane, auto mode) {
+        constexpr int KPL = decltype(keys_per_lane)::value, MODE = decltype(mode)::value;
+        hipLaunchKernelGGL((k_lookupn_probe<36, KPL, MODE>), dim3(grid_for(b.n, kLkThreads * KPL, 256 * 8)),
+                           dim3(kLkThreads), 0, b.st, b.keys, b.n, pv, b.np, b.W, b.out, b.counts, r.slow.p, r.nslow.p);
+        hipLaunchKernelGGL((k_lookupn_fix<36, MODE>), dim3(256), dim3(256), 0, b.st, b.keys, pv, b.np, b.W, b.out,
+                           b.counts, r.slow.p, r.nslow.p);
+    };
+    if (k.ablate == 1)
+        probe(Int<2>{}, Int<1>{});
+    else if (k.ablate == 2)
+        probe(Int<2>{}, Int<2>{});
+    else if (kpl == 1)
+        probe(Int<1>{}, Int<0>{});
+    else if (kpl == 4)
+        probe(Int<4>{}, Int<0>{});
+    else if (kpl == 8)
+        probe(Int<8>{}, Int<0>{});
+    else
+        probe(Int<2>{}, Int<0>{});
+    RP_HIP(hipGetLastError());
+    return true;
 }
 
 static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, uint32_t stride,
@@ -3051,366 +3456,28 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
     if (n == 0) return;
     // the ring is rebuilt on r.st; make the caller's stream wait for it
     if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
+    const LookupKnobs k = lookup_knobs();
     const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const int need = np <= 0 ? 1 : np;
-    const bool use_packed = r.packed && !getenv_flag("RP_RING_WIDE");
-    const char* lay = getenv("RP_RING_LAYOUT");  // A/B: "packed" forces the packed probe kernel
-    const bool use_compact = r.compact && !(lay && !strcmp(lay, "packed")) && !getenv_flag("RP_RING_WIDE");
+    const bool use_packed = r.packed && !k.wide;
+    const bool use_compact = r.compact && !k.layout_packed && !k.wide;
     const bool aligned16 = ((reinterpret_cast<uintptr_t>(keys) & 15) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-    // the LDS-index kernel (round 6; RP_LOOKUP_LDS=0 keeps the lean kernel, 1 forces this one)
-    const char* lds_env = getenv("RP_LOOKUP_LDS");
-    const bool lds_on = lds_env ? !strcmp(lds_env, "1") : kLdsDefault;
-    if (use_compact && lds_on && fixed36 && aligned16 && (uint32_t)need == W && W <= 4 && n >= 64ull * 8 &&
-        !getenv("RP_LOOKUP_ABLATE")) {
-        if (r.lds_pending) ring_build_lds(r);
-        if (r.lds) {
-            RP_REQUIRE(n < (1ull << 32), "lookupn: at most 2^32-1 keys per call");
-            constexpr int KPL = 8;
-            const uint64_t TK = 64ull * KPL, nwt = n / TK, done = nwt * TK;
-            r.slow.reserve(nwt * kSlowPerTile + 1);
-            r.nslow.reserve(nwt + 1);
-            static const int cus = [] {
-                int dev = 0, c = 0;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-                return c > 0 ? c : 256;
-            }();
-            const unsigned g = (unsigned)std::min<uint64_t>((uint64_t)env_pos("RP_LOOKUP_LDS_GRID", (uint64_t)cus),
-                                                            (nwt + kLdsThreads / 64 - 1) / (kLdsThreads / 64));
-            const LdsView lv{r.lent.p, r.lidx.p, r.M, r.lng, r.llg, r.lfb, r.cob,
-                             (uint32_t)(3ull * ((uint64_t)r.M + kEnt3Pad + 6) + 16)};
-            const int stg = (int)env_pos("RP_LOOKUP_LDS_STG", 0) == 1 ? 1 : 0;
-            const int abl = getenv("RP_LOOKUP_LDS_ABL") ? atoi(getenv("RP_LOOKUP_LDS_ABL")) : 0;
-#define RP_LDSK(N, S, A) \
-    hipLaunchKernelGGL((k_lookupn_lds<KPL, N, S, A>), dim3(g), dim3(kLdsThreads), 0, st, keys, nwt, lv, out, counts, r.slow.p, r.nslow.p)
-            if (need == 3 && abl) {  // diagnostics: time ablations (results wrong)
-                switch (abl) {
-                    case 1: RP_LDSK(3, 0, 1); break;
-                    case 2: RP_LDSK(3, 0, 2); break;
-                    case 3: RP_LDSK(3, 0, 3); break;
-                    case 4: RP_LDSK(3, 0, 4); break;
-                    default: RP_LDSK(3, 0, 7); break;
-                }
-            } else if (stg) {
-                switch (need) {
-                    case 1: RP_LDSK(1, 1, 0); break;
-                    case 2: RP_LDSK(2, 1, 0); break;
-                    case 3: RP_LDSK(3, 1, 0); break;
-                    default: RP_LDSK(4, 1, 0); break;
-                }
-            } else {
-                switch (need) {
-                    case 1: RP_LDSK(1, 0, 0); break;
-                    case 2: RP_LDSK(2, 0, 0); break;
-                    case 3: RP_LDSK(3, 0, 0); break;
-                    default: RP_LDSK(4, 0, 0); break;
-                }
-            }
-#undef RP_LDSK
-            RP_HIP(hipGetLastError());
-            const CompactFixView fv{r.tok.p, r.own.p, r.cidx.p, r.view(), r.M, r.ccb};
-            const uint64_t fthreads = nwt * kSlowPerTile;
-            hipLaunchKernelGGL((k_lookupn_fix_tiles<CompactFixView>), dim3((unsigned)((fthreads + 255) / 256)), dim3(256),
-                               0, st, keys, fv, np, W, out, counts, r.slow.p, r.nslow.p, nwt, (uint32_t)TK);
-            RP_HIP(hipGetLastError());
-            if (getenv_flag("RP_LOOKUP_DEBUG")) {
-                std::vector<uint32_t> c(nwt);
-                RP_HIP(hipMemcpyAsync(c.data(), r.nslow.p, 4 * nwt, hipMemcpyDeviceToHost, st));
-                RP_HIP(hipStreamSynchronize(st));
-                uint64_t tot = 0, over = 0;
-                for (uint32_t x : c) {
-                    tot += x;
-                    over += x > kSlowPerTile;
-                }
-                fprintf(stderr, "[rp] lds lookupN: %llu keys, %llu deferred, %llu overflowed tiles (ng %u fb %u ob %u)\n",
-                        (unsigned long long)done, (unsigned long long)tot, (unsigned long long)over, r.lng, r.lfb, r.cob);
-            }
-            if (done < n)
-                launch_lookupn_view(r.view(), keys + done * 36, nullptr, 36, nullptr, n - done, np, W, out + done * W,
-                                    counts ? counts + done : nullptr, st);
-            return;
-        }
-    }
-    if (use_compact && fixed36 && aligned16 && (uint32_t)need == W && W <= 4 && n >= (uint64_t)kLkThreads * 4) {
+    const Batch36 b{keys, n, np, need, W, out, counts, st};  // (read only where fixed36)
+    // whole tiles of keys through 16-byte loads, whole rows of `need` owners through 16-byte stores
+    const bool tiled = use_compact && fixed36 && aligned16 && (uint32_t)need == W && W <= 4;
+    if (tiled && lookupn_lds(r, k, b)) return;
+    if (tiled && n >= (uint64_t)kLkThreads * 4) {
         RP_REQUIRE(n < (1ull << 32), "lookupn: at most 2^32-1 keys per call");
         if (r.chint_pending && need == 3) ring_build_hint(r);
-        const CompactView cv = r.cview();
-        // the wave-specialised kernel (round 6, A/B): RP_LOOKUP_WS = "NP:NC" producer and consumer
-        // waves a workgroup (1:3, 2:6, 1:7, 4:12, 2:2, 1:15, 2:14; "1" = 1:3)
-        const char* ws_env = getenv("RP_LOOKUP_WS");
-        if (ws_env && strcmp(ws_env, "0") && need == 3 && !getenv("RP_LOOKUP_KPL") && cv.ablate == 0 &&
-            n >= 512ull * 4 && n * 12ull < (1ull << 31)) {
-            int wnp = 1, wnc = 3;
-            if (strchr(ws_env, ':') && sscanf(ws_env, "%d:%d", &wnp, &wnc) != 2) wnp = 0;
-            constexpr uint64_t TK = 512;
-            const uint64_t nwt = n / TK, done = nwt * TK;
-            r.slow.reserve(nwt * kSlowPerTile + 1);
-            r.nslow.reserve(nwt + 2);
-            uint32_t* err = r.nslow.p + nwt + 1;
-            RP_HIP(hipMemsetAsync(err, 0, 4, st));
-            static const int cus = [] {
-                int dev = 0, c = 0;
-                (void)hipGetDevice(&dev);
-                (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
-                return c > 0 ? c : 256;
-            }();
-            const uint64_t nwg = (nwt + (uint64_t)wnc - 1) / (uint64_t)(wnc > 0 ? wnc : 1);
-            // workgroups a CU: 16 waves (<= 128 VGPRs), and the LDS (an 18-KB key tile a producer,
-            // kWsSlots 2-KB ring slots and a 768-B list a consumer)
-            const uint64_t lds_wg = (uint64_t)wnp * 18432 + (uint64_t)wnc * (kWsSlots * 2048 + 780);
-            const uint64_t per_cu = wnp + wnc > 0 ? std::max<uint64_t>(1, std::min<uint64_t>(16 / (uint64_t)(wnp + wnc), 163840 / lds_wg)) : 1;
-            const unsigned g = (unsigned)std::min<uint64_t>(nwg, env_pos("RP_LOOKUP_WS_GRID", (uint64_t)cus * per_cu));
-            const int wabl = getenv("RP_LOOKUP_WS_ABL") ? atoi(getenv("RP_LOOKUP_WS_ABL")) : 0;  // diagnostics
-#define RP_WSK(P, C) \
-    hipLaunchKernelGGL((k_lookupn_ws<P, C>), dim3(g), dim3((P + C) * 64), 0, st, keys, nwt, cv, out, (uint32_t)(n * 12ull), counts, r.slow.p, r.nslow.p, err)
-            if (wnp == 1 && wnc == 3)
-                RP_WSK(1, 3);
-            else if (wnp == 2 && wnc == 6)
-                RP_WSK(2, 6);
-            else if (wnp == 1 && wnc == 7)
-                RP_WSK(1, 7);
-            else if (wnp == 4 && wnc == 12 && wabl == 1)
-                hipLaunchKernelGGL((k_lookupn_ws<4, 12, 1>), dim3(g), dim3(16 * 64), 0, st, keys, nwt, cv, out, (uint32_t)(n * 12ull), counts, r.slow.p, r.nslow.p, err);
-            else if (wnp == 4 && wnc == 12 && wabl == 2)
-                hipLaunchKernelGGL((k_lookupn_ws<4, 12, 2>), dim3(g), dim3(16 * 64), 0, st, keys, nwt, cv, out, (uint32_t)(n * 12ull), counts, r.slow.p, r.nslow.p, err);
-            else if (wnp == 4 && wnc == 12)
-                RP_WSK(4, 12);
-            else if (wnp == 2 && wnc == 2)
-                RP_WSK(2, 2);
-            else if (wnp == 1 && wnc == 15)
-                RP_WSK(1, 15);
-            else if (wnp == 2 && wnc == 14)
-                RP_WSK(2, 14);
-            else
-                RP_REQUIRE(false, "RP_LOOKUP_WS: one of 1:3, 2:6, 1:7, 4:12, 2:2, 1:15, 2:14");
-#undef RP_WSK
-            RP_HIP(hipGetLastError());
-            const CompactFixView fv{r.tok.p, r.own.p, r.cidx.p, r.view(), r.M, r.ccb};
-            const uint64_t fthreads = nwt * kSlowPerTile;
-            hipLaunchKernelGGL((k_lookupn_fix_tiles<CompactFixView>), dim3((unsigned)((fthreads + 255) / 256)), dim3(256),
-                               0, st, keys, fv, np, W, out, counts, r.slow.p, r.nslow.p, nwt, (uint32_t)TK);
-            RP_HIP(hipGetLastError());
-            if (getenv_flag("RP_LOOKUP_DEBUG")) {
-                std::vector<uint32_t> c(nwt + 2);
-                RP_HIP(hipMemcpyAsync(c.data(), r.nslow.p, 4 * (nwt + 2), hipMemcpyDeviceToHost, st));
-                RP_HIP(hipStreamSynchronize(st));
-                uint64_t tot = 0, over = 0;
-                for (uint64_t t = 0; t < nwt; t++) {
-                    tot += c[t];
-                    over += c[t] > kSlowPerTile;
-                }
-                fprintf(stderr, "[rp] ws lookupN %d:%d: %llu keys, %llu deferred, %llu overflowed wave-tiles, err %u\n", wnp,
-                        wnc, (unsigned long long)done, (unsigned long long)tot, (unsigned long long)over, c[nwt + 1]);
-            }
-            if (done < n)
-                launch_lookupn_view(r.view(), keys + done * 36, nullptr, 36, nullptr, n - done, np, W, out + done * W,
-                                    counts ? counts + done : nullptr, st);
-            return;
-        }
-        // lookupN(3) (the C2 bench): 8 keys per lane, staged through LDS in four slices (0.925-0.926
-        // against 0.962-0.970 ms for 4 keys per lane; two slices 0.926-0.932; 6 keys per lane
-        // 0.956-0.959; profiles/r02/ab_lookup_lean.json); the other widths 4 keys per lane.
-        // RP_LOOKUP_KPL / RP_LOOKUP_HALF (slices: 2, 4) override (A/B).
-        int kpl = getenv("RP_LOOKUP_KPL") ? atoi(getenv("RP_LOOKUP_KPL")) : (need == 3 ? 8 : 4);
-        if (kpl != 1 && kpl != 2 && !((kpl == 3 || kpl == 8) && need == 3)) kpl = 4;  // the instantiated tiles
-        // The sorted-tile kernel (RP_LOOKUP_SORT = 256 (default) | 512 | 1024 threads, 0 = off): only where
-        // the lean <8, 3, 4> kernel runs by default (lookupN(3) over the hinted index, no other
-        // RP_LOOKUP_* shape knob). It takes the whole tiles of 8 x threads keys; the rest goes on
-        // to the lean kernel's 2,048-key tiles and the generic kernel as before, and one fix pass
-        // covers both (the sorted kernel defers into the same 2,048-key lists).
-        int sort_t = kSortDefault;
-        if (const char* e = getenv("RP_LOOKUP_SORT")) sort_t = atoi(e);
-        RP_REQUIRE(sort_t == 0 || sort_t == 256 || sort_t == 512 || sort_t == 1024, "RP_LOOKUP_SORT: one of 0, 256, 512, 1024");
-        if (need != 3 || !cv.idxh || cv.ablate != 0 || n < 8ull * (uint64_t)sort_t || getenv("RP_LOOKUP_KPL") ||
-            getenv("RP_LOOKUP_HALF") || getenv("RP_LOOKUP_LEAN") || getenv("RP_LOOKUP_STG") || getenv("RP_LOOKUP_LH") ||
-            getenv_flag("RP_LOOKUP_FUSEFIX"))
-            sort_t = 0;
-        const uint64_t stiles = sort_t ? n / (8ull * (uint64_t)sort_t) : 0;
-        const uint64_t s0 = stiles * 8ull * (uint64_t)sort_t;  // keys the sorted kernel takes
-        const uint64_t t0 = s0 / 2048;                         // their 2,048-key lists
-        if (!sort_t && n < (uint64_t)kLkThreads * kpl) kpl = 4;  // at least one whole tile
-        const uint64_t TK = (uint64_t)kLkThreads * kpl;
-        const uint64_t ntiles = (n - s0) / TK, done = s0 + ntiles * TK;
-        r.slow.reserve((t0 + ntiles) * kSlowPerTile + 1);
-        r.nslow.reserve(t0 + ntiles + 1);
-        // the lean kernel's share: the keys after the sorted tiles
-        const uint8_t* const lkeys = keys + s0 * 36;
-        uint32_t* const lout = out + s0 * W;
-        uint8_t* const lcounts = counts ? counts + s0 : nullptr;
-        uint32_t* const lslow = r.slow.p + t0 * kSlowPerTile;
-        uint32_t* const lnslow = r.nslow.p + t0;
-        if (stiles) {
-            // workgroups, tiles strided over them (2^26 C2 keys, profiles/sorted_tiles/grid_sweep.txt):
-            // 256 threads 0.842 ms at 4096 (2048: 0.877, 8192: 0.845, 12288: 0.850); 512 threads 0.890
-            // at 8192 (1024-4096: 0.93-0.95); 1024 threads 0.997 at 512-1024. RP_LOOKUP_GRID overrides (A/B).
-            const unsigned sg = grid_for(stiles, 1, (unsigned)env_pos("RP_LOOKUP_GRID", sort_t == 256 ? 4096u : sort_t == 512 ? 8192u : 1024u));
-#define RP_SORTED(T) \
-    hipLaunchKernelGGL((k_lookupn_sorted<T, 3>), dim3(sg), dim3(T), 0, st, keys, stiles, cv, out, counts, r.slow.p, r.nslow.p)
-            if (sort_t == 256)
-                RP_SORTED(256);
-            else if (sort_t == 512)
-                RP_SORTED(512);
-            else
-                RP_SORTED(1024);
-#undef RP_SORTED
-            RP_HIP(hipGetLastError());
-        }
-        const bool lean = !(getenv("RP_LOOKUP_LEAN") && !strcmp(getenv("RP_LOOKUP_LEAN"), "0"));  // A/B: 0 = round-1 kernel
-        // workgroups, tiles strided over them: the lean kernel at 4096 (4 rounds of the 1024 that
-        // fit, 8 tiles each at C2) ran 0.905-0.911 ms against 0.926-0.930 at 2048 (3072: 0.917;
-        // 5120-16384: 0.908-0.914; profiles/r02/ab_lookup_grid.json). RP_LOOKUP_GRID overrides (A/B).
-        const unsigned g = grid_for(ntiles, 1, (unsigned)env_pos("RP_LOOKUP_GRID", lean ? 4096u : 2048u));
-        const int half = getenv("RP_LOOKUP_HALF") ? atoi(getenv("RP_LOOKUP_HALF")) : (kpl == 8 ? 4 : 0);
-        const CompactFixView fv{r.tok.p, r.own.p, r.cidx.p, r.view(), r.M, r.ccb};
-        // deferred keys finished by the lean kernel's own workgroups (A/B): only <8, 3, 4>
-        const bool fuse = getenv_flag("RP_LOOKUP_FUSEFIX") && lean && half == 4 && kpl == 8 && need == 3 && cv.ablate != 3;
-        const bool stg1 = getenv("RP_LOOKUP_STG") && atoi(getenv("RP_LOOKUP_STG")) == 1 && lean && half == 4 && kpl == 8 &&
-                          need == 3 && !fuse;
-        // RP_LOOKUP_STG=2: asm DMA ring (RP_LOOKUP_STGHS = 4 | 8 key slices; RP_LOOKUP_LH = 1 | 2)
-        const bool stg2 = lean && kpl == 8 && need == 3 && !fuse && getenv("RP_LOOKUP_STG") && atoi(getenv("RP_LOOKUP_STG")) == 2;
-        const int lh = (lean && (half == 4 || stg2) && kpl == 8 && need == 3 && !fuse)
-                           ? (int)env_pos("RP_LOOKUP_LH", stg2 ? 2 : 1) : 1;
-        const int stghs = (int)env_pos("RP_LOOKUP_STGHS", 8);
-#define RP_COMPACT(KPL, NEED)                                                                                  \
-    do {                                                                                                        \
-        if (KPL == 8 && NEED == 3 && stg2 && stghs == 8 && lh == 1)                                             \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 8, false, 2, 1>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
-                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
-        else if (KPL == 8 && NEED == 3 && stg2 && stghs == 8)                                                   \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 8, false, 2, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
-                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
-        else if (KPL == 8 && NEED == 3 && stg2)                                                                 \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 2, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
-                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
-        else if (KPL == 8 && NEED == 3 && stg1 && lh == 2)                                                      \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 1, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
-                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
-        else if (KPL == 8 && NEED == 3 && lh == 2)                                                              \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 0, 2>), dim3(g), dim3(kLkThreads), 0, st, lkeys, \
-                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
-        else if (KPL == 8 && NEED == 3 && stg1)                                                                 \
-            hipLaunchKernelGGL((k_lookupn_lean<8, 3, 4, false, 1>), dim3(g), dim3(kLkThreads), 0, st, lkeys,    \
-                               ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                             \
-        else if (lean && half == 4 && KPL % 4 == 0 && fuse)                                                     \
-            hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED, (KPL % 4 == 0 ? 4 : 1), true>), dim3(g), dim3(kLkThreads), \
-                               0, st, lkeys, ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);               \
-        else if (lean && half == 4 && KPL % 4 == 0)                                                             \
-            hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED, (KPL % 4 == 0 ? 4 : 1)>), dim3(g), dim3(kLkThreads), 0, \
-                               st, lkeys, ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                  \
-        else if (lean && half == 2 && KPL % 2 == 0)                                                             \
-            hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED, (KPL % 2 == 0 ? 2 : 1)>), dim3(g), dim3(kLkThreads), 0, \
-                               st, lkeys, ntiles, cv, lout, lcounts, lslow, lnslow, fv, np);                  \
-        else if (lean)                                                                                          \
-            hipLaunchKernelGGL((k_lookupn_lean<KPL, NEED>), dim3(g), dim3(kLkThreads), 0, st, lkeys, ntiles, cv, \
-                               lout, lcounts, lslow, lnslow, fv, np);                                           \
-        else                                                                                                    \
-            hipLaunchKernelGGL((k_lookupn_compact<KPL, NEED>), dim3(g), dim3(kLkThreads), 0, st, lkeys, ntiles,  \
-                               cv, lout, lcounts, lslow, lnslow);                                               \
-    } while (0)
-#define RP_COMPACT_N(KPL)         \
-    switch (need) {               \
-        case 1: RP_COMPACT(KPL, 1); break; \
-        case 2: RP_COMPACT(KPL, 2); break; \
-        case 3: RP_COMPACT(KPL, 3); break; \
-        default: RP_COMPACT(KPL, 4); break; \
-    }
-        if (ntiles == 0) {  // the sorted kernel took every whole tile
-        } else if (kpl == 1) {
-            RP_COMPACT_N(1);
-        } else if (kpl == 2) {
-            RP_COMPACT_N(2);
-        } else if (kpl == 8 && need == 3) {
-            RP_COMPACT(8, 3);
-        } else if (kpl == 3 && need == 3) {
-            RP_COMPACT(3, 3);
-
-
-        } else {
-            RP_COMPACT_N(4);
-        }
-#undef RP_COMPACT_N
-#undef RP_COMPACT
-        const uint64_t fthreads = (t0 + ntiles) * kSlowPerTile;  // (t0 > 0: TK is 2048, the lists are uniform)
-        if (cv.ablate != 3 && !fuse)
-            hipLaunchKernelGGL((k_lookupn_fix_tiles<CompactFixView>), dim3((unsigned)((fthreads + 255) / 256)),
-                               dim3(256), 0, st, keys, fv, np, W, out, counts, r.slow.p, r.nslow.p, t0 + ntiles,
-                               (uint32_t)TK);
-        RP_HIP(hipGetLastError());
-#ifdef RP_LK_PROF
-        if (getenv_flag("RP_LK_PROF_PRINT")) {
-            unsigned long long v[10];
-            RP_HIP(hipStreamSynchronize(st));
-            RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_lk_prof), sizeof v));
-            const double nw = (double)(v[6] ? v[6] : 1);
-            fprintf(stderr,
-                    "[rp] lean phase cycles per wave-tile (%llu): keys-arrive %.0f hash-all %.0f idx %.0f win1+loop %.0f "
-                    "finish2 %.0f barrier+store %.0f\n",
-                    v[6], v[0] / nw, v[1] / nw, v[2] / nw, v[3] / nw, v[4] / nw, v[5] / nw);
-            memset(v, 0, sizeof v);
-            RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_lk_prof), v, sizeof v));
-            if (stiles) {
-                RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_sk_prof), sizeof v));
-                const double sw = (double)(v[6] ? v[6] : 1);
-                fprintf(stderr,
-                        "[rp] sorted<%d> phase cycles per wave-tile (%llu): keys+hash %.0f sort+deal %.0f idx+win-issue %.0f "
-                        "win1+loop %.0f finish2 %.0f barrier+store %.0f\n",
-                        sort_t, v[6], v[0] / sw, v[1] / sw, v[2] / sw, v[3] / sw, v[4] / sw, v[5] / sw);
-                memset(v, 0, sizeof v);
-                RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_sk_prof), v, sizeof v));
-            }
-        }
-#endif
-        if (getenv_flag("RP_LOOKUP_DEBUG")) {
-            std::vector<uint32_t> c(t0 + ntiles);
-            RP_HIP(hipMemcpyAsync(c.data(), r.nslow.p, 4 * (t0 + ntiles), hipMemcpyDeviceToHost, st));
-            RP_HIP(hipStreamSynchronize(st));
-            uint64_t tot = 0, over = 0;
-            for (uint32_t x : c) {
-                tot += x;
-                over += x > kSlowPerTile;
-            }
-            fprintf(stderr, "[rp] compact lookupN: %llu keys, %llu deferred, %llu overflowed tiles (cb %u ob %u fsh %u sort %d)\n",
-                    (unsigned long long)done, (unsigned long long)tot, (unsigned long long)over, r.ccb, r.cob, r.cfsh, sort_t);
-        }
-        if (done < n)  // the partial last tile
-            launch_lookupn_view(r.view(), keys + done * 36, nullptr, 36, nullptr, n - done, np, W, out + done * W,
-                                counts ? counts + done : nullptr, st);
+        const CompactView cv = r.cview(k);
+        if (!lookupn_ws(r, k, b, cv)) lookupn_compact(r, k, b, cv);
         return;
     }
-    if (use_packed && fixed36 && W <= 4 && need <= 4 && !getenv_flag("RP_RING_NOWINDOW")) {
-        RP_REQUIRE(n < (1ull << 32), "lookupn: at most 2^32-1 keys per call");
-        r.slow.reserve(n + 1);
-        r.nslow.reserve(1);
-        RP_HIP(hipMemsetAsync(r.nslow.p, 0, sizeof(uint32_t), st));
-        const int ablate = getenv("RP_LOOKUP_ABLATE") ? atoi(getenv("RP_LOOKUP_ABLATE")) : 0;
-        const int kpl = getenv("RP_LOOKUP_KPL") ? atoi(getenv("RP_LOOKUP_KPL")) : kDefaultKPL;
-        const PackedView pv = r.pview();
-#define RP_PROBE(KPL, MODE)                                                                                     \
-    hipLaunchKernelGGL((k_lookupn_probe<36, KPL, MODE>), dim3(grid_for(n, kLkThreads * KPL, 256 * 8)),           \
-                       dim3(kLkThreads), 0, st, keys, n, pv, np, W, out, counts, r.slow.p, r.nslow.p);           \
-    hipLaunchKernelGGL((k_lookupn_fix<36, MODE>), dim3(256), dim3(256), 0, st, keys, pv, np, W, out, counts,     \
-                       r.slow.p, r.nslow.p)
-        if (ablate == 1) {
-            RP_PROBE(2, 1);
-        } else if (ablate == 2) {
-            RP_PROBE(2, 2);
-        } else if (kpl == 1) {
-            RP_PROBE(1, 0);
-        } else if (kpl == 4) {
-            RP_PROBE(4, 0);
-        } else if (kpl == 8) {
-            RP_PROBE(8, 0);
-        } else {
-            RP_PROBE(2, 0);
-        }
-#undef RP_PROBE
-        RP_HIP(hipGetLastError());
-        return;
-    }
+    if (use_packed && fixed36 && lookupn_probe(r, k, b)) return;
     if (use_packed)
-        launch_lookupn_view(r.pview(), keys, off, stride, hashes, n, np, W, out, counts, st);
+        launch_lookupn_view(r.pview(), keys, off, stride, hashes, n, np, W, out, counts, st, k.ablate);
     else
-        launch_lookupn_view(r.view(), keys, off, stride, hashes, n, np, W, out, counts, st);
+        launch_lookupn_view(r.view(), keys, off, stride, hashes, n, np, W, out, counts, st, k.ablate);
 }
 
 // ------------------------------------------------------------------- group keys by owner
@@ -4171,12 +4238,6 @@ __global__ __launch_bounds__(256) void k_owner_share(RingView rv, unsigned long 
     if (d) atomicAdd(share + rv.own[i], (unsigned long long)d);
 }
 
-static int load_cus(int device) {
-    int c = 0;
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device);
-    return c > 0 ? c : 256;
-}
-
 // Windows past 64 KB of dynamic LDS need the opt-in, on every device that launches the kernels
 // (`device` is the current device: the handle's). A refusal is an error, not a smaller window.
 static void load_lds_opt_in(int device) {
@@ -4204,7 +4265,7 @@ static void launch_owner_load(const uint32_t* rows, uint64_t slots, uint32_t W, 
     // RP_LOAD_BINS: the window (tests reach the multi-window path with it); never past the LDS
     const uint32_t B = (uint32_t)std::min<uint64_t>(env_pos("RP_LOAD_BINS", kLoadBins), kLoadBins);
     const bool replicate = !(getenv("RP_LOAD_COPIES") && !strcmp(getenv("RP_LOAD_COPIES"), "0"));  // A/B only
-    const int cus = load_cus(device);
+    const int cus = cu_count(device);
     for (uint64_t b0 = 0; b0 < bins; b0 += B) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(B, bins - b0);
         uint32_t cl = 0;
@@ -4787,7 +4848,7 @@ static void route_views(Ring& r, const uint8_t* keys, const uint64_t* off, uint3
     const size_t lds = (size_t)std::min(VBW, PW) * 128u * sizeof(uint32_t);
     const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const RingView rv = r.view();
-    const uint64_t gcap = (uint64_t)load_cus(r.device) * 4;  // 512 threads at <= 64 VGPRs: four workgroups a CU
+    const uint64_t gcap = (uint64_t)cu_count(r.device) * 4;  // 512 threads at <= 64 VGPRs: four workgroups a CU
     for (uint64_t k0 = 0; k0 < n; k0 += kRouteChunk) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(kRouteChunk, n - k0);
         const unsigned g = (unsigned)std::max<uint64_t>(
@@ -4985,7 +5046,7 @@ static void svc_launch(rp::Ring& r, uint32_t last) {
         // RP_SVC_WAVES pollers (one workgroup each, so one an XCD up to 8): see k_lookup_service3
         const uint32_t waves = (uint32_t)std::min<uint64_t>(env_pos("RP_SVC_WAVES", kSvcWaves), 16);
         hipLaunchKernelGGL((k_lookup_service3<RingView>), dim3(waves), dim3(64), 0, r.svc_st, r.svc_dev, r.view(), fv,
-                           r.cview(), r.compact ? 1u : 0u, last, idle, maxt, warm, prof, dt, r.svc_dtb,
+                           r.cview(lookup_knobs()), r.compact ? 1u : 0u, last, idle, maxt, warm, prof, dt, r.svc_dtb,
                            waves > 1 ? (uint32_t)env_pos("RP_SVC_PERIOD", kSvcPeriod) : 0u,
                            (getenv("RP_SVC_ANS") && !strcmp(getenv("RP_SVC_ANS"), "0")) ? 1u : 0u);
     } else
@@ -5503,7 +5564,7 @@ int rp_ring_snap_lookupn_dev(rp_ring_snap* s, const uint8_t* d_keys, const uint6
         RP_HIP(hipSetDevice(s->impl.device));
         const auto [np, W] = rp::replicas(nrep, s->impl.server_count);
         rp::launch_lookupn_view(s->impl.view(), d_keys, d_off, stride, nullptr, n, np, W, d_owners, d_counts,
-                                rp::as_stream(stream));
+                                rp::as_stream(stream), rp::lookup_knobs().ablate);
     });
 }
 
@@ -5807,7 +5868,7 @@ int rp_ring_snap_owner_load_dev(rp_ring_snap* s, const uint8_t* d_keys, const ui
                             [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
                                 rp::launch_lookupn_view(d.view(), stride ? d_keys + k0 * stride : d_keys,
                                                         stride ? nullptr : d_off + k0, stride, nullptr, cnt, rep.np, rep.W,
-                                                        rows, nullptr, st);
+                                                        rows, nullptr, st, rp::lookup_knobs().ablate);
                             });
     });
 }
