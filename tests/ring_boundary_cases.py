@@ -6,6 +6,14 @@ above the last token; tokens 0 and 2^32 - 1; a token in two servers' rows (the f
 buckets of 6, 10, 11 and 15 tokens spread or clustered, and one of 16 (the compact layout is then
 not built).
 
+A case may sit at an id base: that many filler names (`fill-<i>:1`) are interned before its
+servers, by one add_remove call that adds and removes them with distinct caller tokens, so the
+ring is empty again and the servers' ids are id_base + row. The wide variants (WIDE_CASE_NAMES,
+`<case>@<names>`) put three of the token sets on ids of 14, 15, 16 and 17 bits, where the layouts
+change: the LDS index is built up to 14 bits, the compact layout up to 16 with fingerprints of
+24 - ob bits, and at exactly 2^ob names the highest id is all ones in the owner field, so that
+with token 2^32 - 1 a real entry equals the value k_pack3 pads the entries with.
+
 No torch, no GPU: everything derives from the sorted tests' keys, uuid_keys(42, 0, NKEYS), and
 their host hashes H. A case holds the per-server token rows; hash_func() turns them into the
 dict-backed hashFunc of the device HashRing, and the same rows go to the oracle's add_remove, so
@@ -43,17 +51,26 @@ def compact_params(M, nnames):
 
 
 class Case:
-    def __init__(self, name, rows, regime, compact=True, dense=(), ties_per_list=None):
+    def __init__(self, name, rows, regime, compact=True, dense=(), ties_per_list=None, id_base=0):
         self.name = name
+        self.id_base = id_base    # filler names interned before the servers: their ids are id_base + row
         self.rows = np.ascontiguousarray(rows, dtype=np.uint32)  # [servers, R]: server s's tokens in add order
         self.nserv, self.R = self.rows.shape
         self.servers = ["bnd-%d:3000" % s for s in range(self.nserv)]
         self.regime = regime      # "exact": fsh == 0; "fp": fsh > 0
-        self.compact = compact    # False: a bucket of 16 tokens, the compact layout is not built
+        self.compact = compact    # False: a bucket of 16 tokens or ids past 16 bits, the compact layout is not built
         self.dense = list(dense)  # [(bucket, placement, tokens)] of the designed buckets
         self.ties_per_list = ties_per_list  # designed tie keys per whole list, or None
         self.M = len(np.unique(self.rows))  # ring size: a token already in the ring is not inserted again
-        self.cb, self.ob, self.fsh = compact_params(self.M, self.nserv)
+        self.N = id_base + self.nserv  # names interned once the ring is built
+        self.cb, self.ob, self.fsh = compact_params(self.M, self.N)
+
+    def filler_names(self):
+        return ["fill-%d:1" % i for i in range(self.id_base)]
+
+    def filler_tokens(self):
+        """R distinct caller tokens per filler (an odd multiplier permutes the 32-bit values)."""
+        return filler_tokens(0, self.id_base, self.R)
 
     def add_tokens(self):
         """The rows as orc.Ring.add_remove(servers, [], add_tokens, None) takes them."""
@@ -61,7 +78,8 @@ class Case:
 
     def hash_func(self, fallback):
         """hashFunc of the device HashRing: server + str(i) -> rows[server][i]; any other string
-        (the checksum string) goes to `fallback` (farmhash32, as the oracle hashes it)."""
+        (the checksum string) goes to `fallback` (farmhash32, as the oracle hashes it). The fillers
+        never reach it: their tokens go to rp_ring_add_remove as an array (filler_tokens)."""
         table = {s + str(i): int(t) for s, row in zip(self.servers, self.rows) for i, t in enumerate(row)}
         return lambda x: table[x] if x in table else fallback(x)
 
@@ -71,7 +89,7 @@ class Case:
         flat = self.rows.reshape(-1)
         order = np.argsort(flat, kind="stable")
         order = order[np.concatenate([[True], np.diff(flat[order].astype(np.int64)) > 0])]
-        return flat[order], (order // self.R).astype(np.uint32)
+        return flat[order], (self.id_base + order // self.R).astype(np.uint32)
 
     def bucket_counts(self):
         """Tokens per bucket of the compact layout."""
@@ -101,6 +119,11 @@ class Case:
         under, over = H - np.uint32(1), H + np.uint32(1)
         return (np.isin(H, t) | (np.isin(under, t) & (under >> sh == H >> sh)) |
                 (np.isin(over, t) & (over >> sh == H >> sh)))
+
+    def under_ties(self, H):
+        """The one-under kind of tie_keys alone: a token one under the hash, with its fingerprint."""
+        under = H - np.uint32(1)
+        return np.isin(under, self.rows.reshape(-1)) & (under >> np.uint32(self.fsh) == H >> np.uint32(self.fsh))
 
     def must_defer(self, H):
         """A lower bound of the deferred set: a key above the last token (its bucket ends the ring:
@@ -136,6 +159,15 @@ class Case:
         hv, lt = np.flatnonzero(heavy), np.flatnonzero(~heavy)
         if (per <= THIN_HEAVY).all() or len(lt) < THIN_LISTS * LIST or len(hv) < THIN_LISTS * THIN_HEAVY:
             return None
+        if self.id_base and self.ties_per_list:
+            # a wide fingerprint shift makes many undesigned keys heavy: deal the designed one-under
+            # ties over the thin lists first, so that each of them holds some
+            u = np.flatnonzero(self.under_ties(H))
+            rest = np.setdiff1d(hv, u)
+            k = min(len(u) // THIN_LISTS, THIN_HEAVY)
+            head = np.concatenate([np.concatenate([u[l * k:(l + 1) * k], rest[l * (THIN_HEAVY - k):(l + 1) * (THIN_HEAVY - k)]])
+                                   for l in range(THIN_LISTS)])
+            hv = np.concatenate([head, np.setdiff1d(hv, head)])
         order, h0, l0 = [], 0, 0
         for l in range(nlists):
             nh = THIN_HEAVY if l < THIN_LISTS else (len(hv) - THIN_LISTS * THIN_HEAVY) // (nlists - THIN_LISTS)
@@ -200,15 +232,17 @@ def pick(a, k):
     return a[(np.arange(k) * len(a)) // k]
 
 
-def sparse_tokens(H, M):
+def sparse_tokens(H, M, fsh=4):
     """at-fp-sparse: list l of 2,048 consecutive keys has SPARSE_TIES[l] tie keys (spread through the
     list): a token on the key's hash, one under it or one over it in turn, the last two with the
-    key's fingerprint at fsh = 4 (the hash's low 4 bits are neither 0 nor 15). Every other token
+    key's fingerprint at the ring's fsh (the hash's low fsh bits are neither all zeros nor all
+    ones; 4 for the 1,000 names of at-fp-sparse). Every other token
     is a midpoint between neighbouring hashes. A kernel that does not defer the one-under kind
     answers it wrongly, and the lists of 32 ties or fewer do not overflow, so the exact pass
     cannot repair it."""
-    low = H & np.uint32(15)
-    ok = (low != 0) & (low != 15)
+    ones = np.uint32((1 << fsh) - 1)
+    low = H & ones
+    ok = (low != 0) & (low != ones)
     ties = []
     for l, c in enumerate(SPARSE_TIES):
         cand = l * LIST + np.flatnonzero(ok[l * LIST:(l + 1) * LIST])
@@ -301,6 +335,51 @@ def build_cases(H):
 CASE_NAMES = ["at-exact", "at-exact-runs", "at-fp", "at-fp-sparse", "ends-quarter", "ends-sliver", "edge-values",
               "edge-values-pad", "buckets", "buckets-runs", "buckets-fp", "buckets-16"]
 
+# The wide variants: three token sets on 1,000 servers whose ids follow id_base filler names, so
+# that N = id_base + 1000 names are interned: the last count with 14-bit ids (the LDS index may be
+# built), the first with 15, the first with 16, the last
+# with 16 (the highest id is all ones in the owner field) and the first with 17 (no compact layout,
+# no direct table of the service, the packed layout at B = 17). More than 2^24 names (no packed
+# layout either) would take 16 M interned strings: out of a test's reach.
+WIDE_N = [16384, 16385, 32769, 65536, 65537]
+WIDE_SETS = ["at-fp-sparse", "edge-values", "buckets-fp"]
+WIDE_SERVERS = 1000
+WIDE_CASE_NAMES = ["%s@%d" % (s, n) for s in WIDE_SETS for n in WIDE_N]
+# the most names with which the lookup service builds its direct table (it keeps id 0xFFFF free)
+SERVICE_TABLE_CASE = "edge-values@65534"
+
+
+def filler_tokens(first, count, R, avoid=None):
+    """R caller tokens for each of the fillers first .. first + count - 1, all distinct (an odd
+    multiplier permutes the 32-bit values) and none of them in `avoid`."""
+    spare = 0 if avoid is None else len(avoid)
+    t = ((np.arange(first * R, (first + count) * R + spare, dtype=np.uint64) * np.uint64(2654435761)) &
+         np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    if avoid is not None:
+        t = t[~np.isin(t, avoid)]
+    return np.ascontiguousarray(t[:count * R])
+
+
+def build_wide_cases(H):
+    """The wide variants, by name. The ids change neither M nor the tokens of edge-values and
+    buckets-fp; at-fp-sparse designs its ties for the variant's fsh."""
+    te, dup = edge_tokens(H, WIDE_SERVERS, 1)
+    tb, dense = bucket_tokens(H, 11000)
+    out = {}
+    for n in WIDE_N + [int(SERVICE_TABLE_CASE.split("@")[1])]:
+        kw = dict(compact=n <= 65536, id_base=n - WIDE_SERVERS)
+        fsh = compact_params(25000, n)[2]
+        sparse = Case("at-fp-sparse@%d" % n, rows_rr(sparse_tokens(H, 25000, fsh), WIDE_SERVERS), "fp",
+                      ties_per_list=SPARSE_TIES, **kw)
+        assert sparse.fsh == fsh
+        edge = Case("edge-values@%d" % n, rows_rr(te, WIDE_SERVERS), "fp", **kw)
+        edge.dup = dup
+        buckets = Case("buckets-fp@%d" % n, rows_rr(tb, WIDE_SERVERS), "fp", dense=dense, **kw)
+        for c in (sparse, edge, buckets):
+            out[c.name] = c
+    return {name: out[name] for name in WIDE_CASE_NAMES + [SERVICE_TABLE_CASE]}
+
+
 _CACHE = {}
 
 
@@ -314,18 +393,29 @@ def keys_and_hashes(orc):
 
 def cases(orc):
     if "cases" not in _CACHE:
-        _CACHE["cases"] = build_cases(keys_and_hashes(orc)[1])
-        assert list(_CACHE["cases"]) == CASE_NAMES
+        H = keys_and_hashes(orc)[1]
+        _CACHE["cases"] = {**build_cases(H), **build_wide_cases(H)}
+        assert list(_CACHE["cases"]) == CASE_NAMES + WIDE_CASE_NAMES + [SERVICE_TABLE_CASE]
     return _CACHE["cases"]
+
+
+def build_oracle(orc, case):
+    """A new oracle ring of a case: the fillers added and removed in one call (their names stay
+    interned, the ring is empty again), then the servers."""
+    ring = orc.Ring(case.R)
+    if case.id_base:
+        fill, ft = case.filler_names(), case.filler_tokens()
+        assert ring.add_remove(fill, fill, ft, ft)
+        assert ring.token_count() == 0 and ring.server_count() == 0
+    assert ring.add_remove(case.servers, [], case.add_tokens(), None)
+    return ring
 
 
 def oracle_ring(orc, case):
     """The oracle ring of a case, built once."""
     key = ("oracle", case.name)
     if key not in _CACHE:
-        ring = orc.Ring(case.R)
-        assert ring.add_remove(case.servers, [], case.add_tokens(), None)
-        _CACHE[key] = ring
+        _CACHE[key] = build_oracle(orc, case)
     return _CACHE[key]
 
 

@@ -213,3 +213,97 @@ def test_thin_order(orc, hashes, name):
     if c.dense:  # the long buckets' keys that two windows can resolve, in the thin lists
         in_dense = np.isin(hashes >> np.uint32(19), [b for b, _, _ in c.dense])
         assert (in_dense & ~heavy)[order][:rb.THIN_LISTS * rb.LIST].sum() >= 500
+
+
+# -- the wide variants: the same token sets on ids that follow id_base filler names
+
+WIDE_OB = {16384: 14, 16385: 15, 32769: 16, 65534: 16, 65536: 16, 65537: 17}
+SPARSE_FSH = {16384: 8, 16385: 9, 32769: 10, 65536: 10, 65537: 11}  # M = 25,000: cb 14; 4 at 1,000 names
+
+
+@pytest.mark.parametrize("name", rb.WIDE_CASE_NAMES + [rb.SERVICE_TABLE_CASE])
+def test_wide_construction(orc, hashes, name):
+    c = rb.cases(orc)[name]
+    H = hashes
+    base, N = name.split("@")[0], int(name.split("@")[1])
+    narrow = rb.cases(orc)[base]
+    T, O = c.sorted_ring()
+    assert c.N == N == c.id_base + c.nserv and c.nserv == rb.WIDE_SERVERS
+    assert len(T) == c.M and (np.diff(T.astype(np.int64)) > 0).all()
+    # the layout parameters: ids in ob bits, 24 - ob fingerprint bits of the 32 - cb below the bucket
+    cb = int(np.log2(c.M))
+    assert (1 << cb) <= c.M < (2 << cb)
+    assert (c.cb, c.ob, c.fsh) == (cb, WIDE_OB[N], (32 - cb) - (24 - WIDE_OB[N]))
+    assert (1 << (c.ob - 1)) < N <= (1 << c.ob) and c.fsh > 0
+    assert c.compact == (N <= 65536) and c.bucket_counts().max() <= 15
+    assert c.hint_fits()
+    # every id of id_base .. N - 1 owns tokens, the highest one too
+    assert np.array_equal(np.unique(O), np.arange(c.id_base, N))
+    assert (O[1:] != O[:-1]).all()
+    ft = c.filler_tokens()
+    assert len(ft) == c.id_base * c.R and len(np.unique(ft)) == len(ft)
+    assert len(set(c.filler_names())) == c.id_base and not set(c.filler_names()) & set(c.servers)
+    nlists = rb.NKEYS // rb.LIST
+    ties = c.tie_keys(H)
+    deferred, over = c.deferred_lower_bound(H, nlists * rb.LIST)
+    above = int((H[:nlists * rb.LIST] > c.rows.max()).sum())
+    assert deferred == above + int(ties[:nlists * rb.LIST].sum())
+    order = c.thin_order(H)
+    assert order is not None and np.array_equal(np.sort(order), np.arange(rb.NKEYS))
+    heavy = c.heavy_keys(H)
+    assert (heavy | ~c.must_defer(H)).all()
+    per = heavy[order][:nlists * rb.LIST].reshape(nlists, rb.LIST).sum(axis=1)
+    assert (per[:rb.THIN_LISTS] == rb.THIN_HEAVY).all()
+
+    if base == "at-fp-sparse":
+        assert c.fsh == SPARSE_FSH[N] and narrow.fsh == 4 and c.M == narrow.M == 25000
+        per_list = ties[:nlists * rb.LIST].reshape(nlists, rb.LIST).sum(axis=1)
+        assert per_list.tolist() == rb.SPARSE_TIES and ties[nlists * rb.LIST:].sum() == 0
+        on, over_, under = c.on_token(H), np.isin(H + np.uint32(1), T), np.isin(H - np.uint32(1), T)
+        assert np.array_equal(ties, on | over_ | under) and np.array_equal(under, c.under_ties(H))
+        assert [int(x.sum()) for x in (on, under, over_)] == [sum((t - k + 2) // 3 for t in rb.SPARSE_TIES) for k in (0, 1, 2)]
+        assert over >= sum(t > rb.SLOTS for t in rb.SPARSE_TIES) == 4 and over < nlists
+        # the thin lists each hold designed one-under ties: a fast path that does not defer them
+        # leaves a wrong row that no whole-list redo repairs
+        thin_under = under[order][:rb.THIN_LISTS * rb.LIST].reshape(rb.THIN_LISTS, rb.LIST).sum(axis=1)
+        assert (thin_under >= 1).all(), thin_under
+    if base == "edge-values":
+        assert np.array_equal(np.sort(c.rows.reshape(-1)), np.sort(rb.edge_tokens(H, rb.WIDE_SERVERS, 1)[0]))
+        assert T[0] == 0 and T[-1] == NIL and O[-1] == N - 1  # the highest id owns 2^32 - 1
+        assert c.M == c.rows.size - 3 and c.R <= 12
+        for d in c.dup:
+            srv = np.flatnonzero((c.rows == d).any(axis=1))
+            assert d in H and len(srv) == 2 and O[T == d].tolist() == [c.id_base + srv[0]]
+        inner = T[(T != 0) & (T != NIL)]
+        assert 0.2 < (H < inner.min()).mean() < 0.3 and 0.2 < (H > inner.max()).mean() < 0.3
+        rmask = np.uint32((1 << (32 - c.cb)) - 1)
+        ent = (((T & rmask) >> np.uint32(c.fsh)) << np.uint32(c.ob)) | O
+        assert ent.max() < (1 << 24) or not c.compact
+        if N in (16384, 65536):  # ids fill the owner field: the last entry is k_pack3's pad value
+            assert N == 1 << c.ob and np.flatnonzero(ent == 0xFFFFFF).tolist() == [c.M - 1]
+        else:
+            assert not (ent == 0xFFFFFF).any()
+    if base == "buckets-fp":
+        assert np.array_equal(c.rows, narrow.rows) and c.dense == narrow.dense
+        counts = c.bucket_counts()
+        assert all(counts[b] == n for b, _, n in c.dense) and counts.max() == 15
+        assert deferred >= 200 and over == 0
+
+
+@pytest.mark.parametrize("name", rb.WIDE_CASE_NAMES + [rb.SERVICE_TABLE_CASE])
+def test_wide_oracle_vs_numpy_walk(orc, hashes, name):
+    """The oracle after the filler call (one add_remove that adds and removes every filler): the
+    names keep their ids, the ring is the servers' alone, and its rows are the numpy walk's."""
+    c = rb.cases(orc)[name]
+    T, O = c.sorted_ring()
+    oracle = rb.oracle_ring(orc, c)
+    assert oracle.token_count() == c.M and oracle.server_count() == c.nserv
+    assert [oracle.name(c.id_base + i) for i in range(c.nserv)] == c.servers
+    assert [oracle.name(i) for i in (0, c.id_base - 1)] == ["fill-0:1", "fill-%d:1" % (c.id_base - 1)]
+    ot, oo = oracle.dump()
+    assert np.array_equal(ot, T) and np.array_equal(oo, O)
+    for n in (-1, 0, 1, 2, 3, 4):
+        want, wcnt = ref_lookupn(T, O, c.nserv, hashes, n)
+        got, gcnt = rb.oracle_rows(orc, c, n)
+        assert np.array_equal(gcnt, wcnt), n
+        assert np.array_equal(got, want), n
