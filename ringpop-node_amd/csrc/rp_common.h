@@ -109,6 +109,14 @@ inline uint64_t env_pos(const char* name, uint64_t dflt) {
     return (end && *end == 0 && v > 0) ? (uint64_t)v : dflt;
 }
 
+// Compute units of `device` (`dflt` when the query fails). Every caller passes its handle's device,
+// which the C ABI made the current one.
+inline int cu_count(int device, int dflt = 256) {
+    int c = 0;
+    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device);
+    return c > 0 ? c : dflt;
+}
+
 inline unsigned grid_for(uint64_t items, unsigned per_block, unsigned cap = 2048) {
     uint64_t g = (items + per_block - 1) / per_block;
     if (g == 0) g = 1;

@@ -3107,14 +3107,6 @@ static void ring_compute_checksum(Ring& r) {
 // the compact layout's sorted / lean / round-1 kernels, the packed window probe, and then the
 // generic kernels over the packed or the wide view.
 
-// Compute units of `device` (256 when the query fails). Every caller passes its handle's device,
-// which the C ABI made the current one.
-static int cu_count(int device) {
-    int c = 0;
-    (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, device);
-    return c > 0 ? c : 256;
-}
-
 // f(Int<N>{}) for the N = 1..4 owners a row the tiled kernels are built for
 template <int N>
 using Int = std::integral_constant<int, N>;

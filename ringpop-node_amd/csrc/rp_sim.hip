@@ -48,6 +48,7 @@
 #include "rp_names.h"
 #include "rp_philox.h"
 #include "rp_prims.h"
+#include "rp_sim_plan.h"
 #include "rp_swim.h"
 
 namespace rp {
@@ -3618,10 +3619,7 @@ struct Sim {
         return p;
     }
     bool early_pending = false;
-    bool early_on = [] {
-        const char* e = getenv("RP_SIM_EARLY");
-        return e && *e == '1';
-    }();
+    SimKnobs knobs = sim_knobs();  // read again at stage 0 of every round
     DevBuf<uint32_t> elist;
     uint32_t N = 0, NL = 0, v0 = 0, G = 1, shard = 0;
     unsigned grid = 0;
@@ -3672,154 +3670,110 @@ struct Sim {
     DevBuf<int64_t> cs_i64;
     std::vector<uint8_t> cs_obs;
 
-    uint32_t cus = 0;  // compute units of the device (first refresh)
+    uint32_t cus = 0;  // compute units of the device, at least 1 (first use)
+    uint32_t cu() {
+        if (cus == 0) cus = (uint32_t)cu_count(device, 1);
+        return cus;
+    }
+
+    // The chain kernels' launch lines: grid, workgroup and instance of each (rp_sim_plan.h chooses).
+    void launch_ck(CkKernel kn, const uint32_t* sel, const uint32_t* nsel, hipStream_t s) {
+        const uint32_t groups = (NL + 63) / 64;
+        switch (kn) {
+        case CkKernel::None: break;
+        // (the compiler emits the instances in the order of these lines; kept as it was, so that
+        // the device code object stays the same byte for byte)
+        case CkKernel::Pair32:
+            hipLaunchKernelGGL((k_ck_pair<6, 2, 32>), dim3((NL + 31) / 32), dim3(512), 0, s, d, sel, nsel);
+            break;
+        case CkKernel::Pc32: hipLaunchKernelGGL((k_ck_pc<3, 2>), dim3(groups), dim3(256), 0, s, d, sel, nsel); break;
+        case CkKernel::Pc7: hipLaunchKernelGGL(k_ck_pc<7>, dim3(groups), dim3(512), 0, s, d, sel, nsel); break;
+        case CkKernel::Pc3: hipLaunchKernelGGL(k_ck_pc<3>, dim3(groups), dim3(256), 0, s, d, sel, nsel); break;
+        case CkKernel::Lanes:
+            hipLaunchKernelGGL(k_ck_lanes, dim3(grid_for(NL, 256, 1u << 20)), dim3(256), 0, s, d, sel, nsel);
+            break;
+        case CkKernel::Pair16:
+            hipLaunchKernelGGL((k_ck_pair<6, 2, 16>), dim3((NL + 15) / 16), dim3(512), 0, s, d, sel, nsel);
+            break;
+        case CkKernel::Pair8:
+            hipLaunchKernelGGL((k_ck_pair<6, 2, 8>), dim3((NL + 7) / 8), dim3(512), 0, s, d, sel, nsel);
+            break;
+        }
+    }
+
+    // A list of views for the chains: up to NL entries and, behind them, the count the kernel adds to.
+    template <class K>
+    void launch_list(K kernel, DevBuf<uint32_t>& list, unsigned blocks) {
+        list.reserve(NL + 1);
+        RP_HIP(hipMemsetAsync(list.p + NL, 0, 4, st));
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, st, d, list.p, list.p + NL);
+    }
+
+    uint32_t read_count(const uint32_t* n) {  // a host wait
+        uint32_t c = 0;
+        RP_HIP(hipMemcpyAsync(&c, n, 4, hipMemcpyDeviceToHost, st));
+        RP_HIP(hipStreamSynchronize(st));
+        return c;
+    }
+
+    // Dirty views with equal content are marked clean but for one representative (twin_of).
+    void twin_pass() {
+        uint32_t T = 1024;
+        while (T < 2 * NL) T <<= 1;
+        if (twin_cap < T) {
+            twin_key.release();
+            twin_rep.release();
+            twin_key.reserve(T);
+            twin_rep.reserve(T);
+            twin_cap = T;
+        }
+        if (!twin_of.p) {
+            twin_of.reserve(NL);
+            twin_fp.reserve(NL);
+            twin_cnt.reserve(1);
+            RP_HIP(hipMemsetAsync(twin_of.p, 0xFF, 4ull * NL, st));
+            RP_HIP(hipMemsetAsync(twin_cnt.p, 0, 4, st));
+        }
+        RP_HIP(hipMemsetAsync(twin_key.p, 0xFF, 8ull * T, st));
+        RP_HIP(hipMemsetAsync(twin_rep.p, 0xFF, 4ull * T, st));
+        const unsigned gw = grid_for((uint64_t)NL * 64, 256, 4096);
+        const int verify = knobs.twin_verify;
+        hipLaunchKernelGGL(k_twin_fp, dim3(verify ? gw : grid_for(NL, 256, 4096)), dim3(256), 0, st, d, twin_fp.p,
+                           twin_key.p, twin_rep.p, T - 1, verify);
+        hipLaunchKernelGGL(k_twin_check, dim3(gw), dim3(256), 0, st, d, twin_fp.p, twin_key.p, twin_rep.p, T - 1,
+                           twin_of.p, twin_cnt.p);
+        RP_HIP(hipGetLastError());
+    }
+
+    // Every dirty view's checksum. What runs is rp_sim_plan.h's rule on the handle's knobs.
     void refresh_checksums() {
         if (NL == 0) return;
-        // One chain per lane either way. With no more 64-node groups than CUs (a shard, C4) each
-        // group gets a whole CU: its chain wave plus three producer waves (k_ck_pc, ~130 cycles
-        // per chunk). With more groups than CUs the machine is issue-bound on the chunks'
-        // multiplies, and one wave per group without producers (k_ck_lanes) does less work.
-        // RP_SIM_CK=pc|lanes overrides.
-        if (cus == 0) {
-            int dev = 0, n = 0;
-            RP_HIP(hipGetDevice(&dev));
-            RP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-            cus = (uint32_t)(n > 0 ? n : 1);
-        }
-        const uint32_t groups = (NL + 63) / 64;
-        {
-            const char* ab = getenv("RP_SIM_CK_ABLATE");
-            d.ck_ablate = ab && *ab ? (uint32_t)atoi(ab) : 0u;
-        }
+        d.ck_ablate = knobs.ck_ablate;
         hipLaunchKernelGGL(k_count_dirty, dim3(grid_for(NL, 256, 1024)), dim3(256), 0, st, d);
-        const char* m = getenv("RP_SIM_CK");
-        const bool pc = m ? strcmp(m, "lanes") != 0 : groups <= cus;
-        // twins pay on the lane path (C5 on one GPU: 76.7 vs 78.2 ms per round, 31 % fewer
-        // chains); at a shard's size (C4, the producer/consumer path) the two passes cost about
-        // what they save (3.25 vs 3.14 ms), so RP_SIM_TWINS=1 forces them there
-        const char* tw = getenv("RP_SIM_TWINS");
-        const bool twins = tw && *tw ? *tw != '0' : !pc;
-        if (twins) {
-            uint32_t T = 1024;
-            while (T < 2 * NL) T <<= 1;
-            if (twin_cap < T) {
-                twin_key.release();
-                twin_rep.release();
-                twin_key.reserve(T);
-                twin_rep.reserve(T);
-                twin_cap = T;
-            }
-            if (!twin_of.p) {
-                twin_of.reserve(NL);
-                twin_fp.reserve(NL);
-                twin_cnt.reserve(1);
-                RP_HIP(hipMemsetAsync(twin_of.p, 0xFF, 4ull * NL, st));
-                RP_HIP(hipMemsetAsync(twin_cnt.p, 0, 4, st));
-            }
-            RP_HIP(hipMemsetAsync(twin_key.p, 0xFF, 8ull * T, st));
-            RP_HIP(hipMemsetAsync(twin_rep.p, 0xFF, 4ull * T, st));
-            const unsigned gw = grid_for((uint64_t)NL * 64, 256, 4096);
-            // RP_SIM_TWIN_VERIFY=1: recompute every fingerprint from the rows (a check of vfp)
-            const char* tv = getenv("RP_SIM_TWIN_VERIFY");
-            const int verify = tv && *tv && *tv != '0';
-            hipLaunchKernelGGL(k_twin_fp, dim3(verify ? gw : grid_for(NL, 256, 4096)), dim3(256), 0, st, d, twin_fp.p,
-                               twin_key.p, twin_rep.p, T - 1, verify);
-            hipLaunchKernelGGL(k_twin_check, dim3(gw), dim3(256), 0, st, d, twin_fp.p, twin_key.p, twin_rep.p, T - 1,
-                               twin_of.p, twin_cnt.p);
-            RP_HIP(hipGetLastError());
-        }
-        // with twins marked clean, the views left to hash are compacted so that waves hold
-        // only real chains (a wave runs as long as its longest lane)
-        const uint32_t* sel = nullptr;
+        CkPlan plan = ck_plan_begin(knobs, NL, G, cu());
+        if (plan.twins) twin_pass();
+        const uint32_t* sel = nullptr;  // every view in place
         const uint32_t* nsel = nullptr;
-        if (twins) {
-            twin_list.reserve(NL + 1);
-            RP_HIP(hipMemsetAsync(twin_list.p + NL, 0, 4, st));
-            hipLaunchKernelGGL(k_dirty_list, dim3(grid_for(NL, 256, 1024)), dim3(256), 0, st, d, twin_list.p,
-                               twin_list.p + NL);
+        if (plan.list) {
+            launch_list(k_dirty_list, twin_list, grid_for(NL, 256, 1024));
             sel = twin_list.p;
             nsel = twin_list.p + NL;
         }
-        // pc32 (3 producers x 2 chunks per epoch, 41 KB of LDS) puts 3 groups on a CU. On the
-        // lane path it takes the rounds whose compacted dirty views fill at most 3 groups per CU
-        // (C5 on one GPU: median round 64 against 68 ms); the peak rounds, where nearly every
-        // view is dirty and the machine is issue-bound, stay on k_ck_lanes (pc32 there: 111
-        // against 96 ms). Choosing reads the dirty count back (one small copy per round).
-        bool use32 = m && !strcmp(m, "pc32");
-        uint32_t nd_host = 0;
-        bool nd_known = false;
-        if (!m && !pc && sel) {
-            uint32_t nd = 0;
-            RP_HIP(hipMemcpyAsync(&nd, nsel, 4, hipMemcpyDeviceToHost, st));
-            RP_HIP(hipStreamSynchronize(st));
-            nd_host = nd;
-            nd_known = true;
-            static const uint32_t per_cu = [] {  // A/B: RP_SIM_PC32_PER_CU
-                const char* e = getenv("RP_SIM_PC32_PER_CU");
-                return e && *e ? (uint32_t)atoi(e) : 3u;
-            }();
-            use32 = (nd + 63) / 64 <= per_cu * cus;
-        }
-        // Pass 1 of every view to hash, a wave per view, ahead of the producer/consumer kernels,
-        // whose chain wave otherwise walks its 64 views' bitmaps and deviated members before any
-        // chunk is produced (C5: k_ck_pc<3, 2> 375 -> 324 ms over a run for 13 ms of k_pass1).
-        // k_ck_lanes hides its own lane walks behind other waves: there k_pass1 costs more than
-        // it saves (153 against 49 ms), so it stays in the kernel (RP_SIM_PASS1=0|1 overrides).
-        const bool lanes_path = !use32 && !pc && !(m && !strcmp(m, "pair"));
-        const char* p1e = getenv("RP_SIM_PASS1");
-        // The lane path's order (round 6): the views to hash sorted by their string's length delta
-        // (vdt, kept by block_apply), so that a wave's 64 lanes reach their deviated pieces in the
-        // same chunk groups: the fixup path runs for a whole wave when any lane needs it, and in
-        // C5's peak refreshes list order put a fixup in 10-13 % of wave-groups against 3-4 %
-        // sorted (-DRP_CKL_STAT, profiles/r06/r06ab, r06ac); C5 p95 round 78 -> 68 ms (r06ae).
-        // RP_SIM_CK_SORT: 3 (default) that order, 1 = by this round's shifts from a pass-1
-        // launch (slower: the launch), 0 = list order.
-        const char* cks = getenv("RP_SIM_CK_SORT");
-        const int sort_mode = cks && *cks ? atoi(cks) : 3;
-        const bool is_pair = m && !strcmp(m, "pair");
-        // The same order on the producer/consumer paths when this handle is one shard of several
-        // (each rank of a sharded C5 refreshes on them): C5 in 8 shards on one GPU 147.7 -> 142.6
-        // ms per round; C4 on one GPU (not sharded) 2.41 -> 2.46, so not there (profiles/r06/
-        // r06ah, r06ai). RP_SIM_CK_SORT_PC=0|1 overrides.
-        const char* ckp = getenv("RP_SIM_CK_SORT_PC");
-        const bool pc_on = ckp && *ckp ? *ckp == '1' : G > 1;
-        const bool sort_pc = !lanes_path && !is_pair && sort_mode == 3 && pc_on;
-        if (sort_pc && !sel) {
-            twin_list.reserve(NL + 1);
-            RP_HIP(hipMemsetAsync(twin_list.p + NL, 0, 4, st));
-            hipLaunchKernelGGL(k_dirty_list, dim3(grid_for(NL, 256, 1024)), dim3(256), 0, st, d, twin_list.p,
-                               twin_list.p + NL);
-            sel = twin_list.p;
-            nsel = twin_list.p + NL;
-        }
-        const bool sort_sel = (lanes_path || sort_pc) && sel && sort_mode > 0;
-        const bool pre1 = (sort_sel && sort_mode == 1) || (p1e && *p1e ? *p1e != '0' : !lanes_path);
-        if (pre1 && !(m && !strcmp(m, "pair"))) {
+        const uint32_t nd = plan.need_nd ? read_count(nsel) : 0;  // the refresh's one read-back, if any
+        plan = ck_plan_finish(plan, nd);
+        if (plan.pass1) {
             hipLaunchKernelGGL(k_pass1, dim3(grid_for((uint64_t)NL * 64, 256, 4096)), dim3(256), 0, st, d, sel, nsel);
             d.p1_pre = 1;
         }
-        if (sort_sel) {
-            if (!nd_known) {
-                RP_HIP(hipMemcpyAsync(&nd_host, nsel, 4, hipMemcpyDeviceToHost, st));
-                RP_HIP(hipStreamSynchronize(st));
-            }
+        if (plan.sort) {
             ck_sort_key.reserve(NL + 1);
             ck_sort_sel.reserve(NL + 1);
             hipLaunchKernelGGL(k_ck_sort_keys, dim3(grid_for(NL, 256, 1024)), dim3(256), 0, st, d, sel, nsel,
-                               ck_sort_key.p, ck_sort_sel.p, sort_mode == 3 ? 1 : 0);
-            if (nd_host > 1) radix_sort_pairs(ck_sort_key.p, ck_sort_sel.p, nd_host, 0, 32, st, ws);
+                               ck_sort_key.p, ck_sort_sel.p, plan.key_flag);
+            if (plan.radix) radix_sort_pairs(ck_sort_key.p, ck_sort_sel.p, nd, 0, 32, st, ws);
             sel = ck_sort_sel.p;  // (the count stays *nsel)
         }
-        if (m && !strcmp(m, "pair"))  // A/B: the lane-pair chains, 32 views per workgroup
-            hipLaunchKernelGGL((k_ck_pair<6, 2, 32>), dim3((NL + 31) / 32), dim3(512), 0, st, d, sel, nsel);
-        else if (use32)
-            hipLaunchKernelGGL((k_ck_pc<3, 2>), dim3(groups), dim3(256), 0, st, d, sel, nsel);
-        else if (pc && !(m && !strcmp(m, "pc3")))
-            hipLaunchKernelGGL(k_ck_pc<7>, dim3(groups), dim3(512), 0, st, d, sel, nsel);
-        else if (pc)
-            hipLaunchKernelGGL(k_ck_pc<3>, dim3(groups), dim3(256), 0, st, d, sel, nsel);
-        else
-            hipLaunchKernelGGL(k_ck_lanes, dim3(grid_for(NL, 256, 1u << 20)), dim3(256), 0, st, d, sel, nsel);
+        launch_ck(plan.kernel, sel, nsel, st);
 #ifdef RP_CKL_STAT
         if (getenv("RP_CKL_STAT_PRINT")) {
             unsigned long long v[8];
@@ -3834,7 +3788,7 @@ struct Sim {
         }
 #endif
         d.p1_pre = 0;
-        if (twins) hipLaunchKernelGGL(k_twin_copy, dim3(grid_for(NL, 256)), dim3(256), 0, st, d, twin_of.p);
+        if (plan.twins) hipLaunchKernelGGL(k_twin_copy, dim3(grid_for(NL, 256)), dim3(256), 0, st, d, twin_of.p);
         RP_HIP(hipGetLastError());
     }
     // dirty views with equal content hash once (k_twin_*); RP_SIM_TWINS=0|1 overrides
@@ -3966,6 +3920,7 @@ struct Sim {
         const unsigned g = grid;
         switch (k) {
         case 0:
+            knobs = sim_knobs();  // the round's: the refresh, stage 2 and conv_local() use these
             apply_events();
             hipLaunchKernelGGL(k_round_begin, dim3(1), dim3(64), 0, st, d);
             refresh_checksums();
@@ -3981,15 +3936,10 @@ struct Sim {
             import_in(K_RESP);
             if (NL) {
                 hipLaunchKernelGGL(k_phase_c, dim3(g), dim3(kT), 0, st, d);
-                d1list.reserve(NL + 1);
-                RP_HIP(hipMemsetAsync(d1list.p + NL, 0, 4, st));
-                hipLaunchKernelGGL(k_d1_list, dim3(grid_for(NL, 256)), dim3(256), 0, st, d, d1list.p, d1list.p + NL);
-                const bool early = early_on;
+                launch_list(k_d1_list, d1list, grid_for(NL, 256));
+                const bool early = knobs.early;
                 if (early) {  // this round's dirty views except the D1 senders, listed after C
-                    elist.reserve(NL + 1);
-                    RP_HIP(hipMemsetAsync(elist.p + NL, 0, 4, st));
-                    hipLaunchKernelGGL(k_early_list, dim3(grid_for(NL, 256, 1024)), dim3(256), 0, st, d, elist.p,
-                                       elist.p + NL);
+                    launch_list(k_early_list, elist, grid_for(NL, 256, 1024));
                     if (!st2) {
                         RP_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
                         RP_HIP(hipEventCreateWithFlags(&ev_c, hipEventDisableTiming));
@@ -3997,26 +3947,7 @@ struct Sim {
                     }
                     RP_HIP(hipEventRecord(ev_c, st));
                 }
-                // the senders' checksums (their ping-req bodies carry them) as side-by-side chains
-                // first, so D1's workgroups find their views clean
-                // (RP_SIM_D1_CK=pc: k_ck_pc's one lane per view; blockck: a workgroup per sender
-                // inside D1)
-                const char* d1ck = getenv("RP_SIM_D1_CK");
-                if (d1ck && !strcmp(d1ck, "pc"))
-                    hipLaunchKernelGGL(k_ck_pc<7>, dim3((NL + 63) / 64), dim3(512), 0, st, d, d1list.p, d1list.p + NL);
-                else if (!(d1ck && !strcmp(d1ck, "blockck")) && !getenv("RP_SIM_D1_BLOCKCK"))
-                {
-                    static const int vpg = [] {  // A/B: RP_SIM_D1_VPG = 8 | 16
-                        const char* e = getenv("RP_SIM_D1_VPG");
-                        return e && *e ? atoi(e) : 8;
-                    }();
-                    if (vpg == 16)
-                        hipLaunchKernelGGL((k_ck_pair<6, 2, 16>), dim3((NL + 15) / 16), dim3(512), 0, st, d, d1list.p,
-                                           d1list.p + NL);
-                    else
-                        hipLaunchKernelGGL((k_ck_pair<6, 2, 8>), dim3((NL + 7) / 8), dim3(512), 0, st, d, d1list.p,
-                                           d1list.p + NL);
-                }
+                launch_ck(d1_ck_kernel(knobs), d1list.p, d1list.p + NL, st);
                 hipLaunchKernelGGL(k_phase_d1, dim3(g), dim3(kT), 0, st, d, d1list.p, d1list.p + NL);
                 if (early) {
                     // The D1 chains hold a few CUs for milliseconds (one 64-view group per CU);
@@ -4024,12 +3955,7 @@ struct Sim {
                     // round's refresh would otherwise hash after E. A view that D2, D3 or E
                     // changes again is dirty again and is hashed again then.
                     RP_HIP(hipStreamWaitEvent(st2, ev_c, 0));
-                    const uint32_t groups = (NL + 63) / 64;
-                    if (groups <= cus)
-                        hipLaunchKernelGGL(k_ck_pc<7>, dim3(groups), dim3(512), 0, st2, d, elist.p, elist.p + NL);
-                    else
-                        hipLaunchKernelGGL(k_ck_lanes, dim3(grid_for(NL, 256, 1u << 20)), dim3(256), 0, st2, d,
-                                           elist.p, elist.p + NL);
+                    launch_ck(early_ck_kernel(NL, cu()), elist.p, elist.p + NL, st2);
                     RP_HIP(hipGetLastError());
                     RP_HIP(hipEventRecord(ev_early, st2));
                     early_pending = true;
@@ -4879,11 +4805,6 @@ int rp_sim_census(rp_sim* s, const uint8_t* observe, const int64_t* max_ref, uin
             return;
         }
         RP_HIP(hipSetDevice(S.device));
-        if (S.cus == 0) {
-            int n = 0;
-            RP_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, S.device));
-            S.cus = (uint32_t)(n > 0 ? n : 1);
-        }
         S.cs_u8.reserve((uint64_t)NL + N);
         S.cs_u32.reserve(13ull * N + 2ull * NL + 1);  // cnt 4, ring, clear, at | acc, nlow | o_status 4, o_ring, o_at | o_behind
         S.cs_i64.reserve(4ull * N);
@@ -4911,7 +4832,7 @@ int rp_sim_census(rp_sim* s, const uint8_t* observe, const int64_t* max_ref, uin
         // a multiple of the rows a step; RP_CENSUS_ROWS sets the slab (tests: many and ragged slabs)
         constexpr uint32_t kCsPerCu = 4;
         C.ntiles = (S.d.W + rp::kCsWords - 1) / rp::kCsWords;
-        const uint64_t want_slabs = std::max<uint64_t>(1, ((uint64_t)kCsPerCu * S.cus + C.ntiles - 1) / C.ntiles);
+        const uint64_t want_slabs = std::max<uint64_t>(1, ((uint64_t)kCsPerCu * S.cu() + C.ntiles - 1) / C.ntiles);
         uint64_t rows = (NL + want_slabs - 1) / want_slabs;
         rows = (rows + rp::kCsRowsStep - 1) / rp::kCsRowsStep * rp::kCsRowsStep;
         rows = rp::env_pos("RP_CENSUS_ROWS", rows);

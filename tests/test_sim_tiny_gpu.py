@@ -78,6 +78,12 @@ KNOBS = {
     "twins-verify": {"RP_SIM_TWINS": "1", "RP_SIM_TWIN_VERIFY": "1"},
     "early": {"RP_SIM_EARLY": "1"},
     "dlist1": {"RP_SIM_DLIST_BYTES": None},  # per case: 16 bytes a view = 1 piece
+    "ck-lanes-sort0": {"RP_SIM_CK": "lanes", "RP_SIM_CK_SORT": "0"},
+    "ck-lanes-sort1": {"RP_SIM_CK": "lanes", "RP_SIM_CK_SORT": "1"},
+    "ck-pc-sortpc": {"RP_SIM_CK": "pc", "RP_SIM_CK_SORT_PC": "1"},
+    "ck-pc32-twins-sortpc": {"RP_SIM_CK": "pc32", "RP_SIM_TWINS": "1", "RP_SIM_CK_SORT_PC": "1"},
+    "d1-vpg16": {"RP_SIM_D1_VPG": "16"},
+    "d1-blockck-flag": {"RP_SIM_D1_BLOCKCK": "1"},
 }
 
 
@@ -86,7 +92,12 @@ def test_tiny_sim_paths_match_reference_goldens(gpu, monkeypatch, knob):
     """(b) Every simulator path the larger tests name, on the structured families: the D1 scan
     and mixed selection, the three D1 checksum kernels, every refresh kernel with either pass 1,
     the twin pass with its fingerprints verified, the early refresh, and deviated-piece lists of
-    one piece a view (the bitmap fallback). Checksums after every round and the full syncs."""
+    one piece a view (the bitmap fallback), the refresh's list in list order, sorted by this
+    round's shifts and sorted on the producer/consumer kernels, and the D1 senders' chains 16
+    views a workgroup and inside D1. Checksums after every round and the full syncs.
+    (A handle reads RP_SIM_D1_VPG with its other knobs. While the first simulator of a process
+    fixed it for all later ones, "d1-vpg16" passed on k_ck_pair<6, 2, 8> whenever another test had
+    run before it; it now runs k_ck_pair<6, 2, 16>.)"""
     for key, value in KNOBS[knob].items():
         if value is not None:
             monkeypatch.setenv(key, value)

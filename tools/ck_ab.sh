@@ -2,16 +2,15 @@
 # GPU box: C4 and C5 (one GPU) round times per checksum-kernel choice, bench.py's sim legs only.
 # Variants: auto (defaults), d1blk (RP_SIM_D1_BLOCKCK=1: ping-req senders' checksums by one
 # workgroup each inside D1), lanes / pc32 / pc (RP_SIM_CK, twins on).
-# Usage (repo root): tools/ck_ab.sh TAG "auto hw0"
+# Usage (repo root): tools/ck_ab.sh TAG "auto d1blk"
 set -u
 TAG=${1:-ckab}
 OUT=$PWD/gpurun_out/$TAG
 mkdir -p "$OUT"
-for v in ${2:-auto hw0}; do
-  unset RP_SIM_CK RP_SIM_TWINS RP_SIM_HW RP_SIM_D1_BLOCKCK RP_SIM_PC32_PER_CU
+for v in ${2:-auto}; do
+  unset RP_SIM_CK RP_SIM_TWINS RP_SIM_D1_BLOCKCK RP_SIM_PC32_PER_CU
   case $v in
     auto) ;;
-    hw0) export RP_SIM_HW=0 ;;
     d1blk) export RP_SIM_D1_BLOCKCK=1 ;;
     cu2) export RP_SIM_PC32_PER_CU=2 ;;
     cu4) export RP_SIM_PC32_PER_CU=4 ;;
