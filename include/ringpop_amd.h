@@ -378,6 +378,53 @@ int rp_ring_route_views(rp_ring *r, const char *keys, const uint64_t *off, uint3
                         uint64_t *wrong, uint64_t *lost, uint32_t *key_wrong,
                         uint32_t *truth_owner, uint32_t *owners);
 
+/* Routing agreement over the hash space, without keys: on how many of the 2^32 hash values each
+ * view disagrees with the truth. It is to rp_ring_route_views what rp_ring_moved_ranges is to
+ * rp_ring_moved_keys and rp_ring_owner_share to rp_ring_owner_load: exact, deterministic and
+ * independent of any key set. With tok[0 .. M) / own[0 .. M) the ring's sorted arrays
+ * (rp_ring_dump), the interval of position i is the set of hashes whose lookup position is i:
+ * (tok[i-1], tok[i]] for i > 0, and [0, tok[0]] together with (tok[M-1], 2^32-1] for i = 0. Its
+ * length len(i) is what rp_ring_owner_share adds: tok[i] - tok[i-1], and tok[0] + 2^32 - tok[M-1]
+ * for i = 0 (2^32 on a one-token ring); the lengths sum to 2^32. owner(v, h) and t(h) are as
+ * rp_ring_route_views documents them and are constant on every interval, where they equal their
+ * value at h = tok[i]; owner(v, i), t(i) below. Views, d_col, bit, row_stride, id_cap, d_truth
+ * (NULL: every server of r) and d_active mean exactly what they mean there.
+ * Outputs, each nullable:
+ *   wrong[v]      the sum of len(i) over the positions with owner(v, i) != t(i)
+ *   lost[v]       the sum of len(i) over the positions where owner(v, i) is not null and is not
+ *                 allowed by the truth; lost[v] <= wrong[v] <= 2^32
+ *                 Both are uint64[n_views]. accumulate != 0 adds to what they hold, otherwise they
+ *                 are set; inactive views get 0 (are left alone under accumulate).
+ *   pos_wrong[i]  active views with owner(v, i) != t(i), uint32 by token position: where in the
+ *                 hash space the views disagree. Always set, never accumulated. pos_cap is the
+ *                 buffer's capacity in entries and covers the token count (rp_ring_token_count),
+ *                 else RP_EINVAL. With rp_ring_dump it gives the disputed share of the hash
+ *                 space: the sum of len(i) over the positions with pos_wrong[i] > 0.
+ * Results, not errors: n_views == 0; an empty ring (everything 0, nothing is written to
+ * pos_wrong); a truth that allows nobody (t is null everywhere: a view is wrong and lost on all
+ * 2^32 hashes iff it allows anybody). RP_EINVAL with nothing written: a null handle, bit == 0,
+ * id_cap below rp_ring_id_bound, without d_col a row_stride below id_cap, pos_wrong with pos_cap
+ * below the token count, more views than rp_ring_route_views takes. Token collisions need no
+ * extra rule: r's arrays hold distinct tokens, and the walk over them is the definition.
+ * The cost is (tokens) x (n_views / 64) wave steps whatever the views and the truth look like: a
+ * sparse truth or a one-server view costs no more (the wrong / lost bits of position i follow
+ * from those of i + 1 by a generate / propagate recurrence, which is scanned in chunks; DESIGN
+ * §4.2g). RP_SHARE_CHUNK (read once per call) sets the positions a chunk. The planes and the
+ * chunk aggregates live in the ring's routing scratch, allocated when it first grows, never per
+ * call after that. The _dev form is stream-ordered and never syncs with the host, except that a
+ * stream other than the ring's own first waits for the ring's pending rebuilds (as
+ * rp_ring_route_views_dev does). The host form takes host buffers (truth: row_stride bytes) and
+ * is synchronous. */
+int rp_ring_route_share_dev(rp_ring *r, const uint8_t *d_rows, uint64_t row_stride, uint8_t bit,
+                            uint32_t n_views, const uint32_t *d_col, uint32_t id_cap,
+                            const uint8_t *d_truth, const uint8_t *d_active, int accumulate,
+                            uint64_t *d_wrong, uint64_t *d_lost, uint32_t *d_pos_wrong, uint32_t pos_cap,
+                            void *stream);
+int rp_ring_route_share(rp_ring *r, const uint8_t *rows, uint64_t row_stride, uint8_t bit,
+                        uint32_t n_views, const uint32_t *col, uint32_t id_cap,
+                        const uint8_t *truth, const uint8_t *active, int accumulate,
+                        uint64_t *wrong, uint64_t *lost, uint32_t *pos_wrong, uint32_t pos_cap);
+
 /* ------------------------------------------------------------------ Membership
  * Replaces the hot path of lib/membership/index.js Membership: update (249-324) with the
  * Member.evaluateUpdate rules (lib/membership/member.js:71-202) and computeChecksum /
@@ -739,6 +786,14 @@ int rp_sim_routing(rp_sim *s, rp_ring *ring, const char *keys, const uint64_t *o
                    uint32_t *truth_owner);
 int rp_sim_routing_hashes(rp_sim *s, rp_ring *ring, const uint32_t *hashes, uint64_t n, const uint8_t *truth,
                           uint64_t *wrong, uint64_t *lost, uint32_t *key_wrong, uint32_t *truth_owner);
+/* The same without keys, exact over the hash space: rp_ring_route_share_dev on the handle's
+ * stream with the same views, truth and counted nodes as rp_sim_routing (same rules for the ring's
+ * device, the default truth and sharded handles). Host buffers, synchronous; outputs as
+ * rp_ring_route_share documents them, each nullable: wrong / lost [the handle's nodes] in hash
+ * values of the 2^32, pos_wrong [the ring's token count <= pos_cap] by token position (the shards'
+ * pos_wrong add up). */
+int rp_sim_routing_share(rp_sim *s, rp_ring *ring, const uint8_t *truth,
+                         uint64_t *wrong, uint64_t *lost, uint32_t *pos_wrong, uint32_t pos_cap);
 /* Census of every member over the handle's views, on the handle's stream after the rounds queued
  * so far. Observers O: the handle's nodes v with observe[v] != 0 (observe: uint8[N], global, by
  * node id); observe NULL: every local node that is up now (the nodes rp_sim_checksums reports a

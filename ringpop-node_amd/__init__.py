@@ -97,6 +97,9 @@ SIGNATURES = {
                                        _INT, _P, _P, _P, _P, _P, _P]),
     "rp_ring_route_views": (_INT, [_P, _P, _P, _U32, _P, _U64, _P, _U64, ctypes.c_uint8, _U32, _P, _U32, _P, _P, _INT,
                                    _P, _P, _P, _P, _P]),
+    "rp_ring_route_share_dev": (_INT, [_P, _P, _U64, ctypes.c_uint8, _U32, _P, _U32, _P, _P, _INT, _P, _P, _P, _U32,
+                                       _P]),
+    "rp_ring_route_share": (_INT, [_P, _P, _U64, ctypes.c_uint8, _U32, _P, _U32, _P, _P, _INT, _P, _P, _P, _U32]),
     "rp_members_create": (_INT, [_U32, _INT, _P]),
     "rp_members_destroy": (_INT, [_P]),
     "rp_members_intern": (_INT, [_P, _P, _P, _U32, _P]),
@@ -151,6 +154,7 @@ SIGNATURES = {
     "rp_sim_ring_members": (_INT, [_P, _U32, _P]),
     "rp_sim_routing": (_INT, [_P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P, _P]),
     "rp_sim_routing_hashes": (_INT, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
+    "rp_sim_routing_share": (_INT, [_P, _P, _P, _P, _P, _P, _U32]),
     "rp_sim_census": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rp_members_defer_checksum": (_INT, [_P, _INT]),
     "rp_members_checksum_shard": (_INT, [_P, _U32, _U32, _U32]),
@@ -623,8 +627,8 @@ class HashRing:
                                             truth_ptr, active_ptr, int(bool(accumulate)), wrong_ptr, lost_ptr,
                                             key_wrong_ptr, truth_owner_ptr, owners_ptr, stream))
 
-    def _route(self, src, allowed, truth, active, col, owners):
-        k = src.n
+    def _view_args(self, allowed, truth, active, col):
+        """(allowed, col, truth, active, id bound) as contiguous arrays (or None), checked."""
         allowed = np.ascontiguousarray(allowed, dtype=np.uint8)
         if allowed.ndim != 2:
             raise ValueError("allowed must be a [views, columns] matrix")
@@ -648,6 +652,12 @@ class HashRing:
             ac = np.ascontiguousarray(active, dtype=np.uint8)
             if len(ac) != nv:
                 raise ValueError("active must have one entry per view")
+        return allowed, colv, tr, ac, cap
+
+    def _route(self, src, allowed, truth, active, col, owners):
+        k = src.n
+        allowed, colv, tr, ac, cap = self._view_args(allowed, truth, active, col)
+        nv, rs = allowed.shape
         res = {"wrong": np.zeros(nv, dtype=np.uint64), "lost": np.zeros(nv, dtype=np.uint64),
                "key_wrong": np.zeros(k, dtype=np.uint32), "truth_owner": np.full(k, NULL_ID, dtype=np.uint32)}
         if owners:
@@ -674,6 +684,15 @@ class HashRing:
     def route_view_hashes(self, hashes, allowed, truth=None, active=None, col=None, owners=False):
         return self._route(_KeySrc.of_hashes(hashes), allowed, truth, active, col, owners)
 
+    def _name_row(self, names, cap):
+        """uint8[cap] by server id: 1 for the names this ring holds."""
+        r = np.zeros(cap, dtype=np.uint8)
+        for s in names:
+            i = self.server_id(s)
+            if i != NULL_ID:
+                r[i] = 1
+        return r
+
     def routeViews(self, keys, views, truth=None):
         """views: a list of server-name lists (the servers each view's ring holds); truth: one more
         (None: every server of this ring). Returns {"owners": per key the owner name under every
@@ -681,19 +700,55 @@ class HashRing:
         the key counts of route_view_ids}. Names this ring does not hold are ignored."""
         keys = [k if isinstance(k, (bytes, np.ndarray)) else str(k) for k in keys]
         cap = self.id_bound()
-
-        def row(names):
-            r = np.zeros(cap, dtype=np.uint8)
-            for s in names:
-                i = self.server_id(s)
-                if i != NULL_ID:
-                    r[i] = 1
-            return r
-        allowed = np.stack([row(v) for v in views]) if len(views) else np.zeros((0, cap), dtype=np.uint8)
-        res = self.route_view_ids(keys, allowed, truth=None if truth is None else row(truth), owners=True)
+        allowed = np.stack([self._name_row(v, cap) for v in views]) if len(views) else np.zeros((0, cap), dtype=np.uint8)
+        res = self.route_view_ids(keys, allowed, truth=None if truth is None else self._name_row(truth, cap),
+                                  owners=True)
         nm = lambda i: None if i == NULL_ID else self.name(int(i))  # noqa: E731
         return {"owners": [[nm(i) for i in r] for r in res["owners"]], "truth": [nm(i) for i in res["truth_owner"]],
                 "wrong": [int(x) for x in res["wrong"]], "lost": [int(x) for x in res["lost"]]}
+
+    # -- routing agreement over the hash space (no keys: exact shares of the 2^32 hash values)
+    def route_share_dev(self, rows_ptr, row_stride, n_views, bit=1, col_ptr=None, id_cap=None, truth_ptr=None,
+                        active_ptr=None, accumulate=False, wrong_ptr=None, lost_ptr=None, pos_wrong_ptr=None,
+                        pos_cap=0, stream=None):
+        """rp_ring_route_share_dev on device buffers."""
+        check(lib().rp_ring_route_share_dev(self._h, rows_ptr, row_stride, bit, n_views, col_ptr,
+                                            self.id_bound() if id_cap is None else id_cap, truth_ptr, active_ptr,
+                                            int(bool(accumulate)), wrong_ptr, lost_ptr, pos_wrong_ptr, pos_cap,
+                                            stream))
+
+    def route_share_ids(self, allowed, truth=None, active=None, col=None, pos=True):
+        """On how many of the 2^32 hash values every view disagrees with the truth; allowed, truth,
+        active and col as route_view_ids takes them. Returns {"wrong": uint64[views] hash values
+        whose owner under the view is not the truth's, "lost": uint64[views] hash values sent to a
+        server the truth does not allow} and, with pos=True, "pos_wrong": uint32[tokens], the active
+        views that disagree on the interval that ends at each token of dump()."""
+        allowed, colv, tr, ac, cap = self._view_args(allowed, truth, active, col)
+        nv, rs = allowed.shape
+        m = self.size
+        res = {"wrong": np.zeros(nv, dtype=np.uint64), "lost": np.zeros(nv, dtype=np.uint64)}
+        if pos:
+            res["pos_wrong"] = np.zeros(m, dtype=np.uint32)
+        check(lib().rp_ring_route_share(self._h, allowed.ctypes.data if nv else None, rs, 1, nv, _ptr(colv), cap,
+                                        _ptr(tr), _ptr(ac), 0, res["wrong"].ctypes.data if nv else None,
+                                        res["lost"].ctypes.data if nv else None,
+                                        res["pos_wrong"].ctypes.data if pos and m else None, m))
+        return res
+
+    def routeShare(self, views, truth=None):
+        """views: a list of server-name lists, truth: one more (None: every server of this ring),
+        as routeViews takes them. Returns {"wrong" / "lost": per view the hash values (of 2^32) of
+        route_share_ids, "disputed": the hash values on which at least one view disagrees}."""
+        cap = self.id_bound()
+        allowed = np.stack([self._name_row(v, cap) for v in views]) if len(views) else np.zeros((0, cap), dtype=np.uint8)
+        res = self.route_share_ids(allowed, truth=None if truth is None else self._name_row(truth, cap))
+        tok, _ = self.dump()
+        disputed = 0
+        if len(tok):
+            t = tok.astype(np.int64)
+            length = np.diff(t, prepend=t[-1] - (1 << 32))
+            disputed = int(length[res["pos_wrong"] > 0].sum())
+        return {"wrong": [int(x) for x in res["wrong"]], "lost": [int(x) for x in res["lost"]], "disputed": disputed}
 
     # -- owner load and hash-space share (how even is the ring?)
     def id_bound(self):
@@ -1388,6 +1443,22 @@ class GossipSim:
                  res["key_wrong"].ctypes.data if k else None, res["truth_owner"].ctypes.data if k else None)
         return res
 
+    def routingShare(self, ring, truth=None):
+        """`routing` without keys, exact over the hash space (HashRing.route_share_ids): {"wrong",
+        "lost": uint64 per node of this handle, in hash values of the 2^32, "pos_wrong": uint32 per
+        token of ring.dump(), the counted nodes that disagree there}. truth as `routing` takes it."""
+        nl = getattr(self, "NL", self.N)
+        tr = None if truth is None else np.ascontiguousarray(np.asarray(truth) != 0, dtype=np.uint8)
+        if tr is not None and len(tr) != self.N:
+            raise ValueError("truth must have one entry per member")
+        m = ring.size
+        res = {"wrong": np.zeros(nl, dtype=np.uint64), "lost": np.zeros(nl, dtype=np.uint64),
+               "pos_wrong": np.zeros(m, dtype=np.uint32)}
+        check(lib().rp_sim_routing_share(self._h, ring._h, _ptr(tr), res["wrong"].ctypes.data if nl else None,
+                                         res["lost"].ctypes.data if nl else None,
+                                         res["pos_wrong"].ctypes.data if m else None, m))
+        return res
+
     def census(self, observe=None, max_ref=None, want=_CENSUS_FIELDS):
         """Census of every member over this handle's views (rp_sim_census): {"observers": int,
         "status": uint32 [N, 4] (alive, suspect, faulty, leave), "in_ring", "at_max": uint32 [N],
@@ -1545,6 +1616,7 @@ class SimShard:
 
     ring_members = GossipSim.ring_members
     routing = GossipSim.routing
+    routing_share = GossipSim.routingShare
     census = GossipSim.census
 
 
@@ -1664,6 +1736,14 @@ class ShardedGossipSim:
                 "lost": np.concatenate([p["lost"] for p in parts]),
                 "key_wrong": sum((p["key_wrong"] for p in parts[1:]), parts[0]["key_wrong"].copy()),
                 "truth_owner": parts[0]["truth_owner"]}
+
+    def routingShare(self, ring, truth=None):
+        """GossipSim.routingShare over the shards: wrong / lost in node order, pos_wrong summed."""
+        tr = self.default_truth() if truth is None else np.asarray(truth) != 0
+        parts = [s.routing_share(ring, tr) for s in self.shards]
+        return {"wrong": np.concatenate([p["wrong"] for p in parts]),
+                "lost": np.concatenate([p["lost"] for p in parts]),
+                "pos_wrong": sum((p["pos_wrong"] for p in parts[1:]), parts[0]["pos_wrong"].copy())}
 
     def census(self, observe=None):
         """GossipSim.census over the shards, in two phases: the element-wise max of the shards'

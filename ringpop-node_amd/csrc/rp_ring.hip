@@ -2675,6 +2675,7 @@ struct RouteScratch {
     DevBuf<unsigned long long> plane;  // [id bound][view words]: the views that allow each server
     DevBuf<unsigned long long> meta;   // any[view words] | active[view words] | truth allows anybody
     DevBuf<uint8_t> tr;                // per server id: allowed by the truth
+    DevBuf<unsigned long long> scan;   // route_share: aggregates [chunks][4][view words] | carries [chunks][2][view words]
     DevBuf<uint8_t> io8;               // the host form's rows, truth and active bytes
     DevBuf<uint32_t> io32;             // the host form's column map and uint32 outputs
     DevBuf<unsigned long long> io64;   // the host form's wrong | lost
@@ -4865,6 +4866,215 @@ static void route_views(Ring& r, const uint8_t* keys, const uint64_t* off, uint3
     }
 }
 
+// ------------------------------------------------------------- routing agreement over the hash space
+// On how many of the 2^32 hash values every view disagrees with the truth (rp_ring_route_share*),
+// without any key. owner(v, h) and t(h) are constant on the interval of each token position, so
+// the answer is a sum of interval lengths, and the wrong / lost bits of position k follow from
+// those of position k + 1 (cyclically), bitwise in a 64-view plane word:
+//   W_k = (P_k ^ T_k)  | (~P_k & ~T_k & W_{k+1})      P_k: the view allows own[k] (k_route_pack's
+//   L_k = (P_k & ~T_k) | (~P_k        & L_{k+1})      planes), T_k: the truth does (its tr byte)
+// Both are generate / propagate recurrences x_k = g_k | (p_k & x_{k+1}); pairs compose by
+// (g, p) o (g', p') = (g | p & g', p & p'). The ring is cut into chunks of C positions. After
+// k_route_pack, three launches, none of which waits on another workgroup:
+//   k_share_reduce  one thread per (chunk, view word) composes its chunk's (g, p) for W and for L,
+//                   walking the chunk upwards; a wave's lanes are consecutive words of one chunk, so
+//                   its plane reads are contiguous. Eight positions' loads are issued together.
+//   k_share_carry   one thread per view word composes the chunk aggregates from the last chunk to
+//                   the first. The value entering position M - 1 from position 0 is G, the generate
+//                   word of the whole ring: a bit that propagates all the way round has no generate
+//                   anywhere (the view allows nobody, and for W neither does the truth) and is 0.
+//                   Then it writes every chunk's carry-in: the two words entering its last position.
+//   k_share_apply   one wave per (chunk, view word), one lane per view. The wave takes 64 positions
+//                   at a time from the chunk's end: lane j loads position top - 1 - j's owner, truth
+//                   byte, plane word and interval length (one coalesced and one gathered load each),
+//                   and the 64 steps read them lane by lane (v_readlane: wave-uniform). Each lane
+//                   keeps its own W and L bit and adds the length to two uint64 registers; at the end
+//                   of the chunk one 64-bit atomic per non-zero (view, counter). POS: a ballot of
+//                   the active W bits per step, its popcount kept by the step's lane and added to
+//                   pos_wrong with one atomic per position and view word.
+// The cost is M * PW wave steps whatever the views or the truth look like.
+constexpr int kShareThreads = 256;          // k_share_reduce and k_share_apply: four waves
+constexpr int kShareCarryThreads = 64;      // k_share_carry
+constexpr uint32_t kShareMinChunk = 64;     // positions: one batch of k_share_apply
+constexpr uint64_t kShareMaxWords = 1ull << 24;  // chunks * view words the aggregates may take (768 MB)
+
+__global__ __launch_bounds__(kShareThreads) void k_share_reduce(
+    const uint32_t* __restrict__ own, uint32_t M, uint32_t C, const unsigned long long* __restrict__ plane,
+    const uint8_t* __restrict__ tr, uint32_t PW, unsigned long long* __restrict__ agg) {
+    const uint32_t w = (blockIdx.y * (uint32_t)(kShareThreads / 64) + (threadIdx.x >> 6)) * 64u + (threadIdx.x & 63);
+    if (w >= PW) return;
+    const uint32_t c = blockIdx.x;
+    const uint64_t lo = (uint64_t)c * C, hi = lo + C < M ? lo + C : M;
+    unsigned long long gw = 0, pw = ~0ull, gl = 0, pl = ~0ull;
+    for (uint64_t k = lo; k < hi; k += 8) {
+        uint32_t o[8];
+        unsigned long long p[8];
+        uint8_t t[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) o[q] = own[k + q < hi ? k + q : hi - 1];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            p[q] = plane[(uint64_t)o[q] * PW + w];
+            t[q] = tr[o[q]];
+        }
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            if (k + q >= hi) break;
+            const unsigned long long T = t[q] ? ~0ull : 0ull, P = p[q];
+            gw |= pw & (P ^ T);
+            pw &= ~P & ~T;
+            gl |= pl & (P & ~T);
+            pl &= ~P;
+        }
+    }
+    unsigned long long* a = agg + (uint64_t)c * 4u * PW + w;
+    a[0] = gw;
+    a[PW] = pw;
+    a[2ull * PW] = gl;
+    a[3ull * PW] = pl;
+}
+
+__global__ __launch_bounds__(kShareCarryThreads) void k_share_carry(
+    const unsigned long long* __restrict__ agg, uint32_t nchunks, uint32_t PW, unsigned long long* __restrict__ carry) {
+    const uint32_t w = blockIdx.x * (uint32_t)kShareCarryThreads + threadIdx.x;
+    if (w >= PW) return;
+    unsigned long long xw = 0, xl = 0;  // the whole ring's generate words
+#pragma unroll 4
+    for (uint32_t c = nchunks; c-- > 0;) {
+        const unsigned long long* a = agg + (uint64_t)c * 4u * PW + w;
+        xw = a[0] | (a[PW] & xw);
+        xl = a[2ull * PW] | (a[3ull * PW] & xl);
+    }
+#pragma unroll 4
+    for (uint32_t c = nchunks; c-- > 0;) {
+        const unsigned long long* a = agg + (uint64_t)c * 4u * PW + w;
+        carry[(uint64_t)c * 2u * PW + w] = xw;
+        carry[((uint64_t)c * 2u + 1u) * PW + w] = xl;
+        xw = a[0] | (a[PW] & xw);
+        xl = a[2ull * PW] | (a[3ull * PW] & xl);
+    }
+}
+
+__device__ __forceinline__ unsigned long long share_lane64(unsigned long long v, uint32_t j) {
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j);
+    return ((unsigned long long)b << 32) | a;
+}
+
+template <bool POS>
+__global__ __launch_bounds__(kShareThreads) void k_share_apply(
+    RingView rv, uint32_t C, const unsigned long long* __restrict__ plane, const unsigned long long* __restrict__ act,
+    const uint8_t* __restrict__ tr, const unsigned long long* __restrict__ carry, uint32_t PW,
+    unsigned long long* __restrict__ wrong, unsigned long long* __restrict__ lost, uint32_t* __restrict__ pos_wrong) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t w = blockIdx.y * (uint32_t)(kShareThreads / 64) + (threadIdx.x >> 6);
+    if (w >= PW) return;
+    const uint32_t c = blockIdx.x, M = rv.M;
+    const uint64_t lo = (uint64_t)c * C, hi = lo + C < M ? lo + C : M;
+    const bool on = (act[w] >> lane) & 1ull;
+    bool W = (carry[(uint64_t)c * 2u * PW + w] >> lane) & 1ull;
+    bool L = (carry[((uint64_t)c * 2u + 1u) * PW + w] >> lane) & 1ull;
+    unsigned long long aw = 0, al = 0;
+    for (uint64_t top = hi; top > lo;) {
+        const uint32_t cnt = top - lo < 64u ? (uint32_t)(top - lo) : 64u;
+        const uint32_t k = (uint32_t)(top - 1u) - (lane < cnt ? lane : 0u);
+        const uint32_t o = rv.own[k];
+        const uint32_t t = tr[o];
+        const unsigned long long p = plane[(uint64_t)o * PW + w];
+        const uint64_t tk = rv.tok[k];
+        const unsigned long long len = k ? tk - rv.tok[k - 1] : tk + (1ull << 32) - rv.tok[M - 1];
+        uint32_t pc = 0;
+        for (uint32_t j = 0; j < cnt; j++) {
+            const bool P = (share_lane64(p, j) >> lane) & 1ull;
+            if (__builtin_amdgcn_readlane((int)t, (int)j)) {
+                W = !P;
+                L = !P && L;
+            } else {
+                W = P || W;
+                L = P || L;
+            }
+            const unsigned long long lj = share_lane64(len, j);
+            if (on && W) aw += lj;
+            if (on && L) al += lj;
+            if constexpr (POS) {
+                const unsigned long long m = __ballot(on && W);
+                if (lane == j) pc = (uint32_t)__popcll(m);
+            }
+        }
+        if constexpr (POS) {
+            if (lane < cnt && pc) atomicAdd(pos_wrong + k, pc);
+        }
+        top -= cnt;
+    }
+    const uint64_t v = (uint64_t)w * 64u + lane;  // (below n_views wherever `on`)
+    if (aw && wrong) atomicAdd(wrong + v, aw);
+    if (al && lost) atomicAdd(lost + v, al);
+}
+
+// Outputs as rp_ring_route_share_dev documents; everything is queued on st.
+static void route_share(Ring& r, const uint8_t* rows, uint64_t row_stride, uint8_t bit, uint32_t V, const uint32_t* col,
+                        uint32_t id_cap, const uint8_t* truth, const uint8_t* active, int accumulate, uint64_t* wrong,
+                        uint64_t* lost, uint32_t* pos_wrong, uint32_t pos_cap, hipStream_t st) {
+    const uint32_t idb = r.nt.size(), M = r.M;
+    RP_REQUIRE(id_cap >= idb, "route_share: id_cap is below the ring's id bound (rp_ring_id_bound)");
+    RP_REQUIRE(V == 0 || rows, "route_share: null view rows");
+    RP_REQUIRE(bit != 0, "route_share: bit is zero");
+    RP_REQUIRE(V == 0 || col || row_stride >= id_cap, "route_share: without a column map row_stride covers id_cap");
+    RP_REQUIRE(!pos_wrong || pos_cap >= M, "route_share: pos_cap is below the token count");
+    const uint32_t PW = V ? (V + 63u) / 64u : 1u;
+    RP_REQUIRE(PW <= 65535u, "route_share: at most 4,194,240 views a call");
+    const uint64_t knob = env_pos("RP_SHARE_CHUNK", 0);  // positions a chunk (read once per call)
+    // the ring is rebuilt on r.st; make the caller's stream wait for it
+    if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
+    if (!accumulate && V) {
+        if (wrong) RP_HIP(hipMemsetAsync(wrong, 0, (uint64_t)V * 8, st));
+        if (lost) RP_HIP(hipMemsetAsync(lost, 0, (uint64_t)V * 8, st));
+    }
+    if (M == 0) return;  // every owner is null, the truth's too
+    if (pos_wrong) RP_HIP(hipMemsetAsync(pos_wrong, 0, (uint64_t)M * 4, st));
+    if (V == 0 || (!wrong && !lost && !pos_wrong)) return;
+    // chunks: four a compute unit at M = 10^6, at least one batch of k_share_apply each, and no
+    // more aggregates than kShareMaxWords whatever the knob says
+    const uint64_t want = 4ull * cu_count(r.device);
+    uint64_t C = knob ? knob : std::max<uint64_t>(kShareMinChunk, (M + want - 1) / want);
+    C = std::min<uint64_t>(std::max<uint64_t>(C, ((uint64_t)M * PW + kShareMaxWords - 1) / kShareMaxWords), M);
+    const uint32_t nchunks = (uint32_t)((M + C - 1) / C);
+    RouteScratch& ws = r.route_ws;
+    ws.use_on(st);
+    ws.plane.reserve((uint64_t)idb * PW);
+    ws.meta.reserve(2ull * PW + 1);
+    ws.tr.reserve(idb);
+    ws.scan.reserve(6ull * nchunks * PW);
+    unsigned long long* any = ws.meta.p;
+    unsigned long long* act = any + PW;
+    unsigned long long* tany = act + PW;
+    unsigned long long* agg = ws.scan.p;
+    unsigned long long* carry = agg + 4ull * nchunks * PW;
+    RP_HIP(hipMemsetAsync(ws.meta.p, 0, (2ull * PW + 1) * 8, st));
+    hipLaunchKernelGGL(k_route_pack, dim3((idb + kRoutePackThreads - 1) / kRoutePackThreads, PW),
+                       dim3(kRoutePackThreads), 0, st, rows, row_stride, bit, V, col, idb, r.d_inring.p, r.inring_n,
+                       truth, active, PW, ws.plane.p, any, act, tany, ws.tr.p);
+    RP_HIP(hipGetLastError());
+    const RingView rv = r.view();
+    constexpr uint32_t wpb = kShareThreads / 64;
+    hipLaunchKernelGGL(k_share_reduce, dim3(nchunks, ((PW + 63u) / 64u + wpb - 1) / wpb), dim3(kShareThreads), 0, st,
+                       rv.own, M, (uint32_t)C, ws.plane.p, ws.tr.p, PW, agg);
+    RP_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_share_carry, dim3((PW + kShareCarryThreads - 1) / kShareCarryThreads),
+                       dim3(kShareCarryThreads), 0, st, agg, nchunks, PW, carry);
+    RP_HIP(hipGetLastError());
+    const dim3 grid(nchunks, (PW + wpb - 1) / wpb);
+    if (pos_wrong)
+        hipLaunchKernelGGL(k_share_apply<true>, grid, dim3(kShareThreads), 0, st, rv, (uint32_t)C, ws.plane.p, act,
+                           ws.tr.p, carry, PW, reinterpret_cast<unsigned long long*>(wrong),
+                           reinterpret_cast<unsigned long long*>(lost), pos_wrong);
+    else
+        hipLaunchKernelGGL(k_share_apply<false>, grid, dim3(kShareThreads), 0, st, rv, (uint32_t)C, ws.plane.p, act,
+                           ws.tr.p, carry, PW, reinterpret_cast<unsigned long long*>(wrong),
+                           reinterpret_cast<unsigned long long*>(lost), pos_wrong);
+    RP_HIP(hipGetLastError());
+}
+
 }  // namespace rp
 
 // ==================================================================================== C ABI
@@ -4939,6 +5149,49 @@ static DevKeys stage_keys(rp::Ring& r, const KeySrc& k, uint64_t n) {
         d.doff = r.io_off.p;
     }
     return d;
+}
+
+// The routing host forms' views and per-view outputs, staged on r.st through the ring's route
+// scratch: io8 = [rows V * row_stride | truth row_stride | active V], io32 = [col id bound | the
+// caller's `extra` uint32 outputs (out32)], io64 = [wrong V | lost V], which hold the caller's
+// values under accumulate. A null host buffer stays a null pointer. unstage_views queues the
+// copies of wrong / lost back; the caller copies out32 and synchronizes.
+struct DevViews {
+    const uint8_t *rows, *truth, *active;
+    const uint32_t* col;
+    uint32_t* out32;
+    uint64_t *wrong, *lost;
+};
+static DevViews stage_views(rp::Ring& r, const uint8_t* rows, uint64_t row_stride, uint64_t V, const uint32_t* col,
+                            const uint8_t* truth, const uint8_t* active, int accumulate, const uint64_t* wrong,
+                            const uint64_t* lost, uint64_t extra) {
+    rp::RouteScratch& ws = r.route_ws;
+    ws.use_on(r.st);
+    const uint64_t idb = r.nt.size(), rb = V * row_stride;
+    ws.io8.reserve(rb + row_stride + V + 1);
+    uint8_t* drows = ws.io8.p;
+    uint8_t* dtruth = truth ? drows + rb : nullptr;
+    uint8_t* dact = active ? drows + rb + row_stride : nullptr;
+    if (rb) RP_HIP(hipMemcpyAsync(drows, rows, rb, hipMemcpyHostToDevice, r.st));
+    if (truth && row_stride) RP_HIP(hipMemcpyAsync(dtruth, truth, row_stride, hipMemcpyHostToDevice, r.st));
+    if (active && V) RP_HIP(hipMemcpyAsync(dact, active, V, hipMemcpyHostToDevice, r.st));
+    ws.io32.reserve(idb + extra + 1);
+    uint32_t* dcol = col ? ws.io32.p : nullptr;
+    if (col && idb) RP_HIP(hipMemcpyAsync(dcol, col, idb * 4, hipMemcpyHostToDevice, r.st));
+    ws.io64.reserve(2 * V + 1);
+    unsigned long long* dwr = wrong ? ws.io64.p : nullptr;
+    unsigned long long* dlo = lost ? ws.io64.p + V : nullptr;
+    if (accumulate && V) {
+        if (wrong) RP_HIP(hipMemcpyAsync(dwr, wrong, V * 8, hipMemcpyHostToDevice, r.st));
+        if (lost) RP_HIP(hipMemcpyAsync(dlo, lost, V * 8, hipMemcpyHostToDevice, r.st));
+    }
+    return {drows, dtruth, dact, dcol, ws.io32.p + idb, reinterpret_cast<uint64_t*>(dwr),
+            reinterpret_cast<uint64_t*>(dlo)};
+}
+static void unstage_views(rp::Ring& r, const DevViews& dv, uint64_t V, uint64_t* wrong, uint64_t* lost) {
+    if (V == 0) return;
+    if (wrong) RP_HIP(hipMemcpyAsync(wrong, dv.wrong, V * 8, hipMemcpyDeviceToHost, r.st));
+    if (lost) RP_HIP(hipMemcpyAsync(lost, dv.lost, V * 8, hipMemcpyDeviceToHost, r.st));
 }
 
 extern "C" {
@@ -5748,43 +6001,51 @@ int rp_ring_route_views(rp_ring* h, const char* keys, const uint64_t* off, uint3
         RP_REQUIRE(V == 0 || rows, "route_views: null view rows");
         svc_stop(r);
         const DevKeys d = stage_keys(r, hashes ? key_hashes(hashes) : key_bytes(keys, off, stride), n);
-        rp::RouteScratch& ws = r.route_ws;
-        ws.use_on(r.st);
-        // io8 = [rows V * row_stride | truth row_stride | active V]
-        const uint64_t rb = V * row_stride;
-        ws.io8.reserve(rb + row_stride + V + 1);
-        uint8_t* drows = ws.io8.p;
-        uint8_t* dtruth = truth ? drows + rb : nullptr;
-        uint8_t* dact = active ? drows + rb + row_stride : nullptr;
-        if (rb) RP_HIP(hipMemcpyAsync(drows, rows, rb, hipMemcpyHostToDevice, r.st));
-        if (truth && row_stride) RP_HIP(hipMemcpyAsync(dtruth, truth, row_stride, hipMemcpyHostToDevice, r.st));
-        if (active && V) RP_HIP(hipMemcpyAsync(dact, active, V, hipMemcpyHostToDevice, r.st));
-        // io32 = [col idb | key_wrong n | truth_owner n | owners n * V], io64 = [wrong V | lost V]
-        ws.io32.reserve(idb + 2 * n + n * V + 1);
-        uint32_t* dcol = col ? ws.io32.p : nullptr;
-        uint32_t* dkw = key_wrong ? ws.io32.p + idb : nullptr;
-        uint32_t* dto = truth_owner ? ws.io32.p + idb + n : nullptr;
-        uint32_t* dow = owners ? ws.io32.p + idb + 2 * n : nullptr;
-        if (col && idb) RP_HIP(hipMemcpyAsync(dcol, col, idb * 4, hipMemcpyHostToDevice, r.st));
-        ws.io64.reserve(2 * V + 1);
-        unsigned long long* dwr = wrong ? ws.io64.p : nullptr;
-        unsigned long long* dlo = lost ? ws.io64.p + V : nullptr;
-        if (accumulate && V) {
-            if (wrong) RP_HIP(hipMemcpyAsync(dwr, wrong, V * 8, hipMemcpyHostToDevice, r.st));
-            if (lost) RP_HIP(hipMemcpyAsync(dlo, lost, V * 8, hipMemcpyHostToDevice, r.st));
-        }
-        rp::route_views(r, d.dk, d.doff, stride, d.dh, n, drows, row_stride, bit, n_views, dcol, id_cap, dtruth, dact,
-                        accumulate, reinterpret_cast<uint64_t*>(dwr), reinterpret_cast<uint64_t*>(dlo), dkw, dto, dow,
-                        r.st);
-        if (V) {
-            if (wrong) RP_HIP(hipMemcpyAsync(wrong, dwr, V * 8, hipMemcpyDeviceToHost, r.st));
-            if (lost) RP_HIP(hipMemcpyAsync(lost, dlo, V * 8, hipMemcpyDeviceToHost, r.st));
-        }
+        // the uint32 outputs: [key_wrong n | truth_owner n | owners n * V]
+        const DevViews dv = stage_views(r, rows, row_stride, V, col, truth, active, accumulate, wrong, lost,
+                                        2 * n + n * V);
+        uint32_t* dkw = key_wrong ? dv.out32 : nullptr;
+        uint32_t* dto = truth_owner ? dv.out32 + n : nullptr;
+        uint32_t* dow = owners ? dv.out32 + 2 * n : nullptr;
+        rp::route_views(r, d.dk, d.doff, stride, d.dh, n, dv.rows, row_stride, bit, n_views, dv.col, id_cap, dv.truth,
+                        dv.active, accumulate, dv.wrong, dv.lost, dkw, dto, dow, r.st);
+        unstage_views(r, dv, V, wrong, lost);
         if (n) {
             if (key_wrong) RP_HIP(hipMemcpyAsync(key_wrong, dkw, n * 4, hipMemcpyDeviceToHost, r.st));
             if (truth_owner) RP_HIP(hipMemcpyAsync(truth_owner, dto, n * 4, hipMemcpyDeviceToHost, r.st));
             if (owners && V) RP_HIP(hipMemcpyAsync(owners, dow, n * V * 4, hipMemcpyDeviceToHost, r.st));
         }
+        RP_HIP(hipStreamSynchronize(r.st));
+    });
+}
+
+int rp_ring_route_share_dev(rp_ring* h, const uint8_t* d_rows, uint64_t row_stride, uint8_t bit, uint32_t n_views,
+                            const uint32_t* d_col, uint32_t id_cap, const uint8_t* d_truth, const uint8_t* d_active,
+                            int accumulate, uint64_t* d_wrong, uint64_t* d_lost, uint32_t* d_pos_wrong,
+                            uint32_t pos_cap, void* stream) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        svc_stop(r);
+        rp::route_share(r, d_rows, row_stride, bit, n_views, d_col, id_cap, d_truth, d_active, accumulate, d_wrong,
+                        d_lost, d_pos_wrong, pos_cap, rp::as_stream(stream));
+    });
+}
+
+int rp_ring_route_share(rp_ring* h, const uint8_t* rows, uint64_t row_stride, uint8_t bit, uint32_t n_views,
+                        const uint32_t* col, uint32_t id_cap, const uint8_t* truth, const uint8_t* active,
+                        int accumulate, uint64_t* wrong, uint64_t* lost, uint32_t* pos_wrong, uint32_t pos_cap) {
+    return guard([&] {
+        rp::Ring& r = R(h);
+        const uint64_t V = n_views, M = r.M;
+        RP_REQUIRE(id_cap >= r.nt.size(), "route_share: id_cap is below the ring's id bound (rp_ring_id_bound)");
+        RP_REQUIRE(V == 0 || rows, "route_share: null view rows");
+        RP_REQUIRE(!pos_wrong || pos_cap >= M, "route_share: pos_cap is below the token count");
+        svc_stop(r);
+        const DevViews dv = stage_views(r, rows, row_stride, V, col, truth, active, accumulate, wrong, lost, M);
+        rp::route_share(r, dv.rows, row_stride, bit, n_views, dv.col, id_cap, dv.truth, dv.active, accumulate, dv.wrong,
+                        dv.lost, pos_wrong ? dv.out32 : nullptr, pos_cap, r.st);
+        unstage_views(r, dv, V, wrong, lost);
+        if (pos_wrong && M) RP_HIP(hipMemcpyAsync(pos_wrong, dv.out32, M * 4, hipMemcpyDeviceToHost, r.st));
         RP_HIP(hipStreamSynchronize(r.st));
     });
 }

@@ -4689,19 +4689,19 @@ int rp_sim_ring_members(rp_sim* s, uint32_t v, uint8_t* in_ring) {
     });
 }
 
-// Every local node's ring membership as views of `ring`, on the handle's stream: only
-// rp_ring_route_views_dev over the status rows (bit IN_RING), after the queued rounds.
-static void sim_routing(rp::Sim& S, rp_ring* ring, const char* keys, const uint64_t* off, uint32_t stride,
-                        const uint32_t* hashes, uint64_t n, const uint8_t* truth, uint64_t* wrong, uint64_t* lost,
-                        uint32_t* key_wrong, uint32_t* truth_owner) {
+static void ring_call(int rc) {
+    if (rc) throw rp::Error(rc, rp::last_error());
+}
+
+// What both routing calls set up on the handle's stream: the cached column map ring id -> member
+// (S.rt_col), the truth bytes (S.rt_truth; k_sim_truth by default) and the per-node result
+// buffers (S.rt_u64 = [wrong NL | lost NL]). Returns the ring's id bound. `tb` stages a caller's
+// truth and lives until the caller has synchronized the stream.
+static uint32_t sim_routing_setup(rp::Sim& S, rp_ring* ring, const uint8_t* truth, std::vector<uint8_t>& tb) {
     RP_REQUIRE(ring, "sim_routing: null ring handle");
     RP_REQUIRE(rp::ring_device(ring) == S.device, "sim_routing: the ring lives on another device than the simulator");
     RP_REQUIRE(S.G == 1 || truth, "sim_routing: a sharded handle needs the truth (no shard holds every node's own status)");
     RP_REQUIRE(S.G == 1 || S.next_stage == 0, "sim_routing: a sharded handle routes at a round boundary (before stage 0)");
-    RP_REQUIRE(n == 0 || hashes || (keys && (stride || off)), "sim_routing: null key buffer");
-    auto ring_call = [](int rc) {
-        if (rc) throw rp::Error(rc, rp::last_error());
-    };
     uint32_t idb = 0;
     ring_call(rp_ring_id_bound(ring, &idb));
     RP_HIP(hipSetDevice(S.device));
@@ -4721,7 +4721,6 @@ static void sim_routing(rp::Sim& S, rp_ring* ring, const char* keys, const uint6
         S.rt_ring = ring;
         S.rt_bound = idb;
     }
-    std::vector<uint8_t> tb;
     S.rt_truth.reserve(N);
     if (truth) {
         tb.resize(N);
@@ -4732,6 +4731,27 @@ static void sim_routing(rp::Sim& S, rp_ring* ring, const char* keys, const uint6
                            S.dead.p, N, S.rt_truth.p);
         RP_HIP(hipGetLastError());
     }
+    S.rt_u64.reserve(2ull * NL + 1);
+    return idb;
+}
+
+// wrong / lost back to the host, after the ring call (which may have changed the current device)
+static void sim_routing_counts(rp::Sim& S, uint64_t* wrong, uint64_t* lost) {
+    RP_HIP(hipSetDevice(S.device));
+    if (S.NL == 0) return;
+    if (wrong) RP_HIP(hipMemcpyAsync(wrong, S.rt_u64.p, 8ull * S.NL, hipMemcpyDeviceToHost, S.st));
+    if (lost) RP_HIP(hipMemcpyAsync(lost, S.rt_u64.p + S.NL, 8ull * S.NL, hipMemcpyDeviceToHost, S.st));
+}
+
+// Every local node's ring membership as views of `ring`, on the handle's stream: only
+// rp_ring_route_views_dev over the status rows (bit IN_RING), after the queued rounds.
+static void sim_routing(rp::Sim& S, rp_ring* ring, const char* keys, const uint64_t* off, uint32_t stride,
+                        const uint32_t* hashes, uint64_t n, const uint8_t* truth, uint64_t* wrong, uint64_t* lost,
+                        uint32_t* key_wrong, uint32_t* truth_owner) {
+    std::vector<uint8_t> tb;
+    const uint32_t idb = sim_routing_setup(S, ring, truth, tb);
+    RP_REQUIRE(n == 0 || hashes || (keys && (stride || off)), "sim_routing: null key buffer");
+    const uint32_t N = S.N, NL = S.NL;
     const uint8_t* dk = nullptr;
     const uint64_t* doff = nullptr;
     const uint32_t* dh = nullptr;
@@ -4750,18 +4770,13 @@ static void sim_routing(rp::Sim& S, rp_ring* ring, const char* keys, const uint6
             doff = S.rt_off.p;
         }
     }
-    S.rt_u64.reserve(2ull * NL + 1);
     uint64_t* dwr = wrong ? S.rt_u64.p : nullptr;
     uint64_t* dlo = lost ? S.rt_u64.p + NL : nullptr;
     uint32_t* dkw = key_wrong ? S.rt_u32.p : nullptr;
     uint32_t* dto = truth_owner ? S.rt_u32.p + n : nullptr;
     ring_call(rp_ring_route_views_dev(ring, dk, doff, stride, dh, n, S.st_.p, N, rp::IN_RING, NL, S.rt_col.p, idb,
                                       S.rt_truth.p, S.rt_truth.p + S.v0, 0, dwr, dlo, dkw, dto, nullptr, S.st));
-    RP_HIP(hipSetDevice(S.device));
-    if (NL) {
-        if (wrong) RP_HIP(hipMemcpyAsync(wrong, dwr, 8ull * NL, hipMemcpyDeviceToHost, S.st));
-        if (lost) RP_HIP(hipMemcpyAsync(lost, dlo, 8ull * NL, hipMemcpyDeviceToHost, S.st));
-    }
+    sim_routing_counts(S, wrong, lost);
     if (n) {
         if (key_wrong) RP_HIP(hipMemcpyAsync(key_wrong, dkw, n * 4, hipMemcpyDeviceToHost, S.st));
         if (truth_owner) RP_HIP(hipMemcpyAsync(truth_owner, dto, n * 4, hipMemcpyDeviceToHost, S.st));
@@ -4781,6 +4796,27 @@ int rp_sim_routing_hashes(rp_sim* s, rp_ring* ring, const uint32_t* hashes, uint
     return guard([&] {
         RP_REQUIRE(n == 0 || hashes, "sim_routing_hashes: null hash buffer");
         sim_routing(SM(s), ring, nullptr, nullptr, 0, hashes, n, truth, wrong, lost, key_wrong, truth_owner);
+    });
+}
+
+int rp_sim_routing_share(rp_sim* s, rp_ring* ring, const uint8_t* truth, uint64_t* wrong, uint64_t* lost,
+                         uint32_t* pos_wrong, uint32_t pos_cap) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        std::vector<uint8_t> tb;
+        const uint32_t idb = sim_routing_setup(S, ring, truth, tb);
+        uint32_t M = 0;
+        ring_call(rp_ring_token_count(ring, &M));
+        RP_REQUIRE(!pos_wrong || pos_cap >= M, "sim_routing_share: pos_cap is below the ring's token count");
+        RP_HIP(hipSetDevice(S.device));
+        S.rt_u32.reserve((uint64_t)M + 1);
+        ring_call(rp_ring_route_share_dev(ring, S.st_.p, S.N, rp::IN_RING, S.NL, S.rt_col.p, idb, S.rt_truth.p,
+                                          S.rt_truth.p + S.v0, 0, wrong ? S.rt_u64.p : nullptr,
+                                          lost ? S.rt_u64.p + S.NL : nullptr, pos_wrong ? S.rt_u32.p : nullptr, M,
+                                          S.st));
+        sim_routing_counts(S, wrong, lost);
+        if (pos_wrong && M) RP_HIP(hipMemcpyAsync(pos_wrong, S.rt_u32.p, 4ull * M, hipMemcpyDeviceToHost, S.st));
+        RP_HIP(hipStreamSynchronize(S.st));
     });
 }
 

@@ -318,6 +318,16 @@ HashRing.prototype.routeViews = function routeViews(keys, views, truth) {
         lost: Array.prototype.slice.call(r.lost)};
 };
 
+// The same without keys, exact over the hash space: routeShare(views, truth) gives {wrong / lost:
+// per view on how many of the 2^32 hash values its owner is another server than the truth's / a
+// server the truth does not hold, disputed: on how many at least one view disagrees}. Numbers: 2^32
+// is exact in a double.
+HashRing.prototype.routeShare = function routeShare(views, truth) {
+    var r = native.ringRouteShare(this._h, views, truth === undefined ? null : truth);
+    return {wrong: Array.prototype.slice.call(r.wrong), lost: Array.prototype.slice.call(r.lost),
+        disputed: r.disputed};
+};
+
 // Range hand-off, and planning a change before any key exists: movedRanges(snap, n) gives the hash
 // intervals [lo, hi] (inclusive, ascending, maximal runs of one pair of rows) on which lookupN(h, n)
 // differs between the snapshot and the ring now, in one device pass over the two token sets and

@@ -740,6 +740,41 @@ static int route_row(napi_env env, rp_ring *r, napi_value names, uint8_t *row, u
     return 0;
 }
 
+/* The byte matrix of views (an array of arrays of server names) and the truth's row (names, or
+ * nullish: NULL) by server id, with the ring's id bound; the row stride is max(bound, 1). The
+ * caller frees *rows and *truth. 0, or -1 with a pending JS exception and nothing to free. */
+static int route_rows(napi_env env, rp_ring *r, napi_value views, napi_value tnames, uint32_t *bound, uint32_t *nv,
+                      uint8_t **rows, uint8_t **truth) {
+    *rows = *truth = NULL;
+    if (rp_ring_id_bound(r, bound)) {
+        napi_throw_error(env, "ERR_RINGPOP_AMD", rp_last_error());
+        return -1;
+    }
+    bool isarr = false;
+    napi_is_array(env, views, &isarr);
+    if (!isarr) {
+        napi_throw_type_error(env, NULL, "views must be an array of arrays of server names");
+        return -1;
+    }
+    napi_get_array_length(env, views, nv);
+    const size_t rs = *bound ? *bound : 1;
+    *rows = (uint8_t *)calloc((size_t)(*nv ? *nv : 1) * rs, 1);
+    if (!is_nullish(env, tnames)) *truth = (uint8_t *)calloc(rs, 1);
+    int bad = *truth ? route_row(env, r, tnames, *truth, *bound) : 0;
+    for (uint32_t v = 0; v < *nv && !bad; v++) {
+        napi_value e;
+        napi_get_element(env, views, v, &e);
+        bad = route_row(env, r, e, *rows + (size_t)v * rs, *bound);
+    }
+    if (bad) {
+        free(*rows);
+        free(*truth);
+        *rows = *truth = NULL;
+        return -1;
+    }
+    return 0;
+}
+
 /* ringRouteViews(h, keys[] | Uint32Array hashes, views: [[server names]], truth: [names] | null) ->
  * {views, wrong, lost: Float64Array[views], keyWrong, truthOwner: Uint32Array[keys],
  * owners: Uint32Array[keys * views]}: every key's owner under every view of this ring at once
@@ -749,34 +784,10 @@ static napi_value js_ring_route_views(napi_env env, napi_callback_info info) {
     handle_t *h = get_handle(env, argv[0], 1);
     if (!h) return NULL;
     rp_ring *r = (rp_ring *)h->p;
-    uint32_t bound = 0;
-    RP_OK(rp_ring_id_bound(r, &bound));
-    bool isarr = false;
-    napi_is_array(env, argv[2], &isarr);
-    if (!isarr) {
-        napi_throw_type_error(env, NULL, "views must be an array of arrays of server names");
-        return NULL;
-    }
-    uint32_t nv = 0;
-    napi_get_array_length(env, argv[2], &nv);
+    uint32_t bound = 0, nv = 0;
+    uint8_t *rows = NULL, *truth = NULL;
+    if (route_rows(env, r, argv[2], argv[3], &bound, &nv, &rows, &truth)) return NULL;
     const size_t rs = bound ? bound : 1;
-    uint8_t *rows = (uint8_t *)calloc((size_t)(nv ? nv : 1) * rs, 1), *truth = NULL;
-    for (uint32_t v = 0; v < nv; v++) {
-        napi_value e;
-        napi_get_element(env, argv[2], v, &e);
-        if (route_row(env, r, e, rows + (size_t)v * rs, bound)) {
-            free(rows);
-            return NULL;
-        }
-    }
-    if (!is_nullish(env, argv[3])) {
-        truth = (uint8_t *)calloc(rs, 1);
-        if (route_row(env, r, argv[3], truth, bound)) {
-            free(rows);
-            free(truth);
-            return NULL;
-        }
-    }
     bool is_typed = false;
     napi_is_typedarray(env, argv[1], &is_typed);
     size_t n = 0;
@@ -834,6 +845,56 @@ static napi_value js_ring_route_views(napi_env env, napi_callback_info info) {
     free(truth);
     free(wrong);
     free(kw);
+    RP_OK(rc);
+    return out;
+}
+
+/* ringRouteShare(h, views: [[server names]], truth: [names] | null) -> {wrong, lost:
+ * Float64Array[views], posWrong: Uint32Array[tokens], disputed}: on how many of the 2^32 hash
+ * values every view disagrees with the truth, per token position how many views do
+ * (rp_ring_route_share), and the hash values on which at least one does (the interval lengths of
+ * rp_ring_dump's tokens where posWrong > 0). The shares are Numbers: at most 2^32, exact in a
+ * double. */
+static napi_value js_ring_route_share(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    handle_t *h = get_handle(env, argv[0], 1);
+    if (!h) return NULL;
+    rp_ring *r = (rp_ring *)h->p;
+    uint32_t bound = 0, nv = 0, m = 0;
+    RP_OK(rp_ring_token_count(r, &m));
+    uint8_t *rows = NULL, *truth = NULL;
+    if (route_rows(env, r, argv[1], argv[2], &bound, &nv, &rows, &truth)) return NULL;
+    const size_t vv = nv ? nv : 1;
+    uint64_t *wrong = (uint64_t *)calloc(2 * vv, 8), *lost = wrong + vv;
+    uint32_t *pw = (uint32_t *)calloc(3 * (size_t)(m ? m : 1), 4), *tok = pw + (m ? m : 1), *own = tok + (m ? m : 1);
+    int rc = rp_ring_route_share(r, rows, bound ? bound : 1, 1, nv, NULL, bound, truth, NULL, 0, wrong, lost, pw, m);
+    if (!rc) rc = rp_ring_dump(r, tok, own, m);
+    napi_value out = NULL;
+    if (!rc) {
+        uint64_t disputed = 0;
+        for (uint32_t i = 0; i < m; i++)
+            if (pw[i]) disputed += i ? (uint64_t)tok[i] - tok[i - 1] : (uint64_t)tok[0] + (1ull << 32) - tok[m - 1];
+        void *dw = NULL, *dl = NULL, *dp = NULL;
+        napi_value vw = new_typed(env, napi_float64_array, nv, 8, &dw);
+        napi_value vl = new_typed(env, napi_float64_array, nv, 8, &dl);
+        napi_value vp = new_typed(env, napi_uint32_array, m, 4, &dp);
+        for (uint32_t v = 0; v < nv; v++) {
+            ((double *)dw)[v] = (double)wrong[v];
+            ((double *)dl)[v] = (double)lost[v];
+        }
+        if (m) memcpy(dp, pw, 4 * (size_t)m);
+        napi_create_object(env, &out);
+        napi_set_named_property(env, out, "wrong", vw);
+        napi_set_named_property(env, out, "lost", vl);
+        napi_set_named_property(env, out, "posWrong", vp);
+        napi_value vd;
+        napi_create_double(env, (double)disputed, &vd);
+        napi_set_named_property(env, out, "disputed", vd);
+    }
+    free(rows);
+    free(truth);
+    free(wrong);
+    free(pw);
     RP_OK(rc);
     return out;
 }
@@ -1792,6 +1853,7 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringMovedKeys", NULL, js_ring_moved_keys, NULL, NULL, NULL, napi_default, NULL},
         {"ringHandoff", NULL, js_ring_handoff, NULL, NULL, NULL, napi_default, NULL},
         {"ringRouteViews", NULL, js_ring_route_views, NULL, NULL, NULL, napi_default, NULL},
+        {"ringRouteShare", NULL, js_ring_route_share, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerLoad", NULL, js_ring_owner_load, NULL, NULL, NULL, napi_default, NULL},
         {"ringOwnerShare", NULL, js_ring_owner_share, NULL, NULL, NULL, napi_default, NULL},
         {"ringMovedRanges", NULL, js_ring_moved_ranges, NULL, NULL, NULL, napi_default, NULL},
