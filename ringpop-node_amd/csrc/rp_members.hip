@@ -18,6 +18,7 @@
 #include "../../include/ringpop_amd.h"
 #include "rp_damp.h"
 #include "rp_hashlong.h"
+#include "rp_members_plan.h"
 #include "rp_names.h"
 #include "rp_swim.h"
 
@@ -454,17 +455,10 @@ __global__ __launch_bounds__(1024) void k_fold_ovf(const uint32_t* __restrict__ 
 //   k_bk_gather  turns back into batch order, from res2[ids[j]] (1 MB, L2-resident), four
 //                changes per lane. The new status / incarnation outputs are copied from the
 //                input by k_bk_scatter (unless they alias it); the fold rewrites local overrides.
-#ifndef RP_BK_BITS
-#define RP_BK_BITS 12
-#endif
+// kBk (ids per bucket), kBkTile (changes per scatter tile), kBkMin and kBkMaxBuckets: rp_members_plan.h
 #ifndef RP_BK_FT
 #define RP_BK_FT 512
 #endif
-constexpr uint32_t kBkBits = RP_BK_BITS, kBk = 1u << kBkBits;  // ids per bucket (4,096: 64 KB of rows)
-#ifndef RP_BK_TILE
-#define RP_BK_TILE 4096
-#endif
-constexpr uint32_t kBkTile = RP_BK_TILE;                       // changes per scatter tile
 constexpr uint32_t kBkST = 1024;                               // threads per scatter tile
 constexpr uint32_t kBkFT = RP_BK_FT;                           // threads per fold workgroup
 #ifndef RP_BK_DUP
@@ -473,7 +467,6 @@ constexpr uint32_t kBkFT = RP_BK_FT;                           // threads per fo
 constexpr uint32_t kBkDup = RP_BK_DUP;  // repeated-address changes a bucket sorts in LDS (1 % repeats: ~80)
 static_assert(kBkDup <= kBkFT && kBkDup <= 1024, "k_bk_fold: one repeated change per thread, 10-bit entry in the key");
 static_assert(kBk % kBkFT == 0 && kBkFT % 64 == 0, "k_bk_fold: whole ids per lane");
-constexpr uint32_t kBkMaxBuckets = 2048;               // (LDS of the scatter tiles): 8M ids
 constexpr uint8_t kResLocal = 4;                       // result: the local override rewrote (status, inc)
 constexpr uint8_t kResRep = 8;                         // repeated changes, results in resj
 static_assert(RP_BK_BITS + (RP_BK_TILE > 4096 ? 13 : 12) <= 30, "bucket-local id + tile-relative index + status in 32 bits");
@@ -976,10 +969,6 @@ __global__ void k_set_apply(const uint32_t* __restrict__ mark, const uint32_t* _
 //   16-byte words; the last tile records the slot's meta. Gated off (*gate == 0), tile 0 only
 //   records the meta.
 
-static bool getenv_on(const char* name) {
-    const char* v = getenv(name);
-    return v && *v && *v != '0';
-}
 constexpr uint32_t kMckStage = 24576;  // LDS bytes a tile's pieces are assembled in
 
 // One member's piece: row, length and (for names of at most 28 bytes plus alignment) the
@@ -1279,13 +1268,12 @@ struct Members {
     // instead of per batch. The slots form ngroups groups of group_slots; a full group is hashed on
     // a side stream (ck_st) while the next batches fold and build their strings into the next
     // group, so up to ngroups - 1 groups of chains overlap the folds. Reads flush and wait. The
-    // slot count is what fits RP_MEMBERS_CK_BYTES (default 6 GiB of HBM), at most kMaxSlots.
+    // slot count is what fits RP_MEMBERS_CK_BYTES (default 6 GiB of HBM), at most kMaxSlots
+    // (ck_pool of rp_members_plan.h).
     // Groups of 512 (round 6; RP_MEMBERS_GROUP_SLOTS overrides): the packed chain kernel
     // (k_hash_long_pack, 16 strings a workgroup) hashes 16 to 512 strings of 3.6 MB in the same
     // ~4 ms, so the chains of a 512-batch group cost no more than a 128-batch one did (rounds 2-5:
-    // a workgroup a string, groups of 128, 2 GiB; 1.00-1.07 G updates/s against 0.86 with groups
-    // of 64 then).
-    static constexpr uint32_t kMaxSlots = 1024, kGroupSlots = 512, kMaxGroups = 4;
+    // a workgroup a string, groups of 128, 2 GiB).
     uint32_t nslots = 1, group_slots = 1, ngroups = 1;
     DevBuf<uint8_t> ck_buf;   // nslots strings of slot_bytes
     uint64_t slot_bytes = 0;
@@ -1308,31 +1296,28 @@ struct Members {
     bool group_busy[kMaxGroups] = {};  // this group's last hash may still be running
     uint32_t slot_index(uint32_t j) const { return cur_group * group_slots + j; }
     DevBuf<uint32_t> ck_len, ck_pos;
-    DevBuf<uint32_t> sk, sv;
+    DevBuf<uint32_t> sk, sv;  // the sorted fold's and set's sorted ids and batch indices
+    // The environment (rp_members_plan.h), as of this handle's creation or its last update, set or
+    // checksum call, whichever came last: refresh_knobs() at the top of each.
+    MemberKnobs knobs = members_knobs();
+    void refresh_knobs() { knobs = members_knobs(); }
     // the grouped (sort-free) fold: per id inline slots for repeated addresses, per change its
-    // rank among its address's changes (RP_MEMBERS_SORTED_FOLD=1 always sorts)
-    bool grouped_fold = !getenv_on("RP_MEMBERS_SORTED_FOLD");
+    // rank among its address's changes
     DevBuf<uint32_t> g_slots;
     DevBuf<uint8_t> g_rk;
     DevBuf<uint32_t> g_part;  // per-workgroup applied counts of k_fold_fast (per bucket: k_bk_fold)
-    // the bucket path (batches of kBkMin changes or more without damp scoring; RP_MEMBERS_BUCKET_FOLD
-    // = 0 | 1 overrides the size rule)
+    // the bucket path (fold_plan: batches of kBkMin changes or more without damp scoring)
     DevBuf<uint32_t> bk_seg;
     DevBuf<BRec> bk_recs;
     DevBuf<int64_t> bk_tb;  // per scatter tile: the compact records' incarnation base, or kBkWide
     DevBuf<uint32_t> bk_res2;  // the bucket fold's 2-bit per-id results (k_bk_gather)
     DevBuf<uint8_t> bk_resj;
-    static constexpr uint32_t kBkMin = 1u << 19;
-    // RP_MEMBERS_FUSE=1 (A/B, off by default): k_link_fold for a grid that is resident at once
-    // with half the machine to spare (its grid barrier needs every workgroup running). Measured
-    // slower: the C3 fold 0.098-0.102 ms against 0.021 for the two launches, the batch 115-119
-    // against 39 us (profiles/r04/r04s): the barrier's agent-scope release / acquire (an L2
-    // write-back and invalidate per wave, since the XCDs' L2s are not coherent) costs far more
-    // than the launch it saves.
+    // k_link_fold (MemberKnobs::fuse) needs a grid that is resident at once, with half the machine
+    // to spare: its grid barrier waits for every workgroup. Measured slower than the two launches:
+    // the barrier's agent-scope release / acquire (an L2 write-back and invalidate per wave, since
+    // the XCDs' L2s are not coherent) costs far more than the launch it saves.
     int fuse_cap = -1;
-    bool fuse_fold(uint32_t g1, hipStream_t s) {
-        const char* e = getenv("RP_MEMBERS_FUSE");
-        if (!e || *e != '1') return false;
+    bool fuse_fits(uint32_t g1) {
         if (fuse_cap < 0) {
             int dev = 0, cus = 0, nbl = 0;
             RP_HIP(hipGetDevice(&dev));
@@ -1340,18 +1325,7 @@ struct Members {
             RP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbl, reinterpret_cast<const void*>(k_link_fold), 256, 0));
             fuse_cap = cus * nbl / 2;
         }
-        if ((int)g1 > fuse_cap) return false;
-        if (!ws.err.p) {
-            ws.err.reserve(1);
-            RP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(uint32_t), s));
-        }
-        return true;
-    }
-    bool use_bucket_fold(uint32_t k, uint32_t nb) const {
-        if (damp_on || nb > kBkMaxBuckets || k >= (1u << 29) || !grouped_fold) return false;
-        const char* e = getenv("RP_MEMBERS_BUCKET_FOLD");
-        if (e && *e) return *e != '0';
-        return k >= kBkMin;
+        return (int)g1 <= fuse_cap;
     }
     DevBuf<uint32_t> mk, mpos;  // set: merge marks and their positions
     // host-buffer staging
@@ -1422,157 +1396,155 @@ struct Members {
         }
     }
 
-    // Everything below is stream-ordered on `s` and never syncs with the host.
-    // Grouped path (every batch size): k_link + k_fold_fast + k_fold_ovf (gated on the overflow
-    // word on the device: it folds only addresses with more than kSlots + 1 changes, and sums
-    // the applied count into n_applied_out). RP_MEMBERS_SORTED_FOLD=1: radix sort + k_fold.
+    void ensure_err(hipStream_t s) {  // the kernels' error word, zeroed when it is first needed
+        if (ws.err.p) return;
+        ws.err.reserve(1);
+        RP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(uint32_t), s));
+    }
+    void zero_counts(uint32_t* n_applied_out, hipStream_t s) {  // a batch that folds nothing applies nothing
+        RP_HIP(hipMemsetAsync(napplied.p, 0, sizeof(uint32_t), s));
+        if (n_applied_out) RP_HIP(hipMemsetAsync(n_applied_out, 0, sizeof(uint32_t), s));
+    }
+    uint32_t pending_history() const {  // pending strings that will append a history entry
+        uint32_t n = 0;
+        for (uint64_t w : pend_mask.w) n += (uint32_t)__builtin_popcountll(w);
+        return n;
+    }
+#ifdef RP_BK_PROF
+    // k_bk_fold's phase cycle counters and per-workgroup timeline on stderr (RP_BK_PROF_PRINT); waits for s
+    void bk_prof_print(uint32_t nb, hipStream_t s) {
+        unsigned long long v[8];
+        RP_HIP(hipStreamSynchronize(s));
+        RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_bk_prof), sizeof v));
+        const double nw = (double)(v[4] ? v[4] : 1);
+        fprintf(stderr, "[rp] k_bk_fold cycles per workgroup (%llu): records %.0f dup-heads %.0f rows+map %.0f dups+count %.0f\n",
+                v[4], v[0] / nw, v[1] / nw, v[2] / nw, v[3] / nw);
+        memset(v, 0, sizeof v);
+        RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_bk_prof), v, sizeof v));
+        // per-workgroup timeline (the grid's quantization): starts and ends in us
+        // from the first start; how many workgroups run at each tenth of the span
+        std::vector<unsigned long long> wg(2 * kBkMaxBuckets);
+        RP_HIP(hipMemcpyFromSymbol(wg.data(), HIP_SYMBOL(g_bk_wg), sizeof(unsigned long long) * 2 * nb));
+        unsigned long long t0 = ~0ull, t1 = 0;
+        std::vector<double> st(nb), du(nb);
+        for (uint32_t i = 0; i < nb; i++) {
+            t0 = std::min(t0, wg[2 * i]);
+            t1 = std::max(t1, wg[2 * i + 1]);
+        }
+        for (uint32_t i = 0; i < nb; i++) {
+            st[i] = (wg[2 * i] - t0) / 100.0;
+            du[i] = (wg[2 * i + 1] - wg[2 * i]) / 100.0;
+        }
+        std::vector<double> ss = st, dd = du;
+        std::sort(ss.begin(), ss.end());
+        std::sort(dd.begin(), dd.end());
+        const double span = (t1 - t0) / 100.0;
+        fprintf(stderr, "[rp] k_bk_fold workgroups %u: span %.1f us; starts p50 %.1f p75 %.1f p90 %.1f last %.1f; "
+                        "durations min %.1f p50 %.1f p90 %.1f max %.1f; running at tenths:",
+                nb, span, ss[nb / 2], ss[nb * 3 / 4], ss[nb * 9 / 10], ss[nb - 1], dd[0], dd[nb / 2], dd[nb * 9 / 10],
+                dd[nb - 1]);
+        for (int q = 0; q < 10; q++) {
+            const double t = span * (q + 0.5) / 10.0;
+            int c = 0;
+            for (uint32_t i = 0; i < nb; i++) c += (st[i] <= t && st[i] + du[i] > t) ? 1 : 0;
+            fprintf(stderr, " %d", c);
+        }
+        fprintf(stderr, "\n");
+    }
+#endif
+
+    // Everything below is stream-ordered on `s` and never syncs with the host. Which kernels fold
+    // the batch is fold_plan's answer (rp_members_plan.h):
+    //   grouped (every batch size): k_link + k_fold_fast;
+    //   bucket (large batches): k_bk_scatter + k_bk_fold;
+    //   sorted: radix sort + k_fold.
+    // The first two end in the overflow step (gated on the overflow word on the device: it folds
+    // only addresses with more than kSlots + 1 changes, and sums the applied count into
+    // n_applied_out), which the checksum string's length launch carries when a string is built.
     // ranged (rp_members_update_range_dev): only the changes whose id lies in [id_lo, id_hi), whole
     // buckets of kBk ids, through the bucket path; no checksum (the rows outside are not this
     // handle's to keep current).
     void update_dev(const uint32_t* ids, const uint8_t* chs, const int64_t* chi, uint32_t k, int64_t now_ms,
                     uint8_t* applied, uint8_t* nst, int64_t* ninc, uint32_t* n_applied_out, hipStream_t s,
                     bool ranged = false, uint32_t id_lo = 0, uint32_t id_hi = 0) {
+        refresh_knobs();
+        const FoldPlan p = fold_plan(knobs, k, cap, nt.size(), damp_on, ranged, id_lo, id_hi, pw.on, pw.st == s);
         if (ranged) {
             RP_REQUIRE(id_lo % kBk == 0 && (id_hi % kBk == 0 || id_hi >= cap) && id_lo <= id_hi,
                        "update_range: the range must be whole buckets of 4,096 ids");
-            RP_REQUIRE(!damp_on && grouped_fold && (cap + kBk - 1) / kBk <= kBkMaxBuckets && k < (1u << 29),
+            RP_REQUIRE(p.path == FoldPath::Bucket || p.path == FoldPath::Empty,
                        "update_range: needs the bucket fold (no damp scoring, at most 8M ids)");
         }
         if (s != st) RP_HIP(hipStreamSynchronize(st));
         if (!k) {
             d_out_k = 0;  // the last batch is now this empty one: damp_last has no scores to hand back
-            RP_HIP(hipMemsetAsync(napplied.p, 0, sizeof(uint32_t), s));
-            if (n_applied_out) RP_HIP(hipMemsetAsync(n_applied_out, 0, sizeof(uint32_t), s));
+            zero_counts(n_applied_out, s);
             return;
         }
-        if (pw.on && (ranged || pw.st != s || use_bucket_fold(k, (cap + kBk - 1) / kBk) || !grouped_fold ||
-                      getenv_on("RP_MEMBERS_FUSE")))
-            drain_write();  // only the grouped fold's launch carries a deferred string
+        if (p.drain) drain_write();
         if (damp_on) {
             d_out.reserve(k);
             d_exc.reserve(k);
             d_out_k = k;
         }
-        if (!ws.err.p) {
-            ws.err.reserve(1);
-            RP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(uint32_t), s));
-        }
+        ensure_err(s);
         const FoldArgs A{chs, chi, rows.p, rcnt.p, ws.err.p, local_id, now_ms, applied, nst, ninc, napplied.p,
                          damp_args(true)};
-        int bits = 8;
-        while (bits < 32 && (1ull << bits) < nt.size()) bits += 8;
-        sk.reserve(k);
-        sv.reserve(k);
         uint32_t* ovf = napplied.p + 1;
-        uint32_t* done = napplied.p + 2;
-        const unsigned g = grid_for(k, 256);
         const bool mine = ck_nsh <= 1 || batch_no % ck_nsh == ck_sh;
         const bool build = !defer_ck && mine && !ranged;
-        if (build && hist_cap && nt.size()) {  // refuse before anything is applied
-            uint32_t pend = 0;
-            for (uint64_t w : pend_mask.w) pend += (uint32_t)__builtin_popcountll(w);
-            if (hist_n + pend + 1 > hist_cap)
-                throw Error(RP_ESTATE, "checksum history full (history_cap of rp_members_checksum_shard): read and "
-                                       "drain it with rp_members_checksum_history_drain");
-        }
+        if (build && hist_cap && nt.size() && hist_n + pending_history() + 1 > hist_cap)  // refuse before anything is applied
+            throw Error(RP_ESTATE, "checksum history full (history_cap of rp_members_checksum_shard): read and "
+                                   "drain it with rp_members_checksum_history_drain");
         batch_no++;
-        const uint32_t nb = (cap + kBk - 1) / kBk;
-        const uint32_t b_lo = ranged ? std::min(nb, id_lo / kBk) : 0u;
-        const uint32_t b_hi = ranged ? (uint32_t)std::min<uint64_t>(nb, ((uint64_t)id_hi + kBk - 1) / kBk) : nb;
-        if (ranged && b_lo >= b_hi) {  // a range past the table (a rank with no ids yet): nothing to fold
-            RP_HIP(hipMemsetAsync(napplied.p, 0, sizeof(uint32_t), s));
-            if (n_applied_out) RP_HIP(hipMemsetAsync(n_applied_out, 0, sizeof(uint32_t), s));
+        if (p.path == FoldPath::Empty) {  // a range past the table (a rank with no ids yet)
+            zero_counts(n_applied_out, s);
             return;
         }
-        if (ranged || use_bucket_fold(k, nb)) {
-            const uint32_t ntiles = (k + kBkTile - 1) / kBkTile;
-            bk_seg.reserve((uint64_t)((nb + 15) / 16) * 16 * ntiles);
-            bk_recs.reserve((uint64_t)ntiles * kBkTile);
-            bk_res2.reserve((uint64_t)nb * kBk / 16);
+        if (p.path == FoldPath::Bucket) {
+            bk_seg.reserve((uint64_t)((p.nb + 15) / 16) * 16 * p.ntiles);
+            bk_recs.reserve((uint64_t)p.ntiles * kBkTile);
+            bk_res2.reserve((uint64_t)p.nb * kBk / 16);
             bk_resj.reserve(k);
-            g_part.reserve(nb + 1);
-            bk_tb.reserve(ntiles);
-            const bool rec8 = !(getenv("RP_BK_REC8") && !strcmp(getenv("RP_BK_REC8"), "0"));  // A/B: 0 = 12-B always
-            // workgroups of the scatter (A/B: RP_BK_SGRID; 0 or >= ntiles: one tile each)
-            const uint32_t sg = (uint32_t)env_pos("RP_BK_SGRID", 0);
-            if (sg && sg < ntiles)
-                hipLaunchKernelGGL(k_bk_scatter<true>, dim3(sg), dim3(kBkST), 0, s, ids, chs, chi, k, nb, ntiles,
-                                   bk_recs.p, bk_seg.p, rec8 ? bk_tb.p : nullptr, nst, ninc, ws.err.p, b_lo, b_hi);
+            g_part.reserve(p.nb + 1);
+            bk_tb.reserve(p.ntiles);
+            int64_t* const tb = p.rec8 ? bk_tb.p : nullptr;
+            const auto scatter = [&](auto kern, uint32_t grid) {
+                hipLaunchKernelGGL(kern, dim3(grid), dim3(kBkST), 0, s, ids, chs, chi, k, p.nb, p.ntiles, bk_recs.p,
+                                   bk_seg.p, tb, nst, ninc, ws.err.p, p.b_lo, p.b_hi);
+            };
+            const auto fold = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3((p.b_hi - p.b_lo + 7) / 8 * 8), dim3(kBkFT), 0, s, bk_recs.p, bk_seg.p, tb,
+                                   p.ntiles, p.nb, p.b_lo, p.b_hi, A, bk_res2.p, bk_resj.p, ovf, g_part.p);
+            };
+            const auto gather = [&](auto kern, uint32_t lanes) {
+                hipLaunchKernelGGL(kern, dim3(grid_for(lanes, 256, 1u << 30)), dim3(256), 0, s, ids, bk_res2.p,
+                                   bk_resj.p, k, applied);
+            };
+            if (p.sgrid)
+                scatter(k_bk_scatter<true>, p.sgrid);
             else
-                hipLaunchKernelGGL(k_bk_scatter<false>, dim3(ntiles), dim3(kBkST), 0, s, ids, chs, chi, k, nb, ntiles,
-                                   bk_recs.p, bk_seg.p, rec8 ? bk_tb.p : nullptr, nst, ninc, ws.err.p, b_lo, b_hi);
-            const bool direct = ranged || !(getenv("RP_BK_DIRECT") && !strcmp(getenv("RP_BK_DIRECT"), "0"));
-            if (ranged) RP_HIP(hipMemsetAsync(g_part.p, 0, sizeof(uint32_t) * (nb + 1), s));  // other ranks' buckets
-            const dim3 fg((b_hi - b_lo + 7) / 8 * 8);
-            if (direct)
-                hipLaunchKernelGGL(k_bk_fold<true>, fg, dim3(kBkFT), 0, s, bk_recs.p, bk_seg.p, rec8 ? bk_tb.p : nullptr,
-                                   ntiles, nb, b_lo, b_hi, A, bk_res2.p, bk_resj.p, ovf, g_part.p);
+                scatter(k_bk_scatter<false>, p.ntiles);
+            if (ranged) RP_HIP(hipMemsetAsync(g_part.p, 0, sizeof(uint32_t) * (p.nb + 1), s));  // other ranks' buckets
+            if (p.direct)
+                fold(k_bk_fold<true>);
             else
-                hipLaunchKernelGGL(k_bk_fold<false>, fg, dim3(kBkFT), 0, s, bk_recs.p, bk_seg.p, rec8 ? bk_tb.p : nullptr,
-                                   ntiles, nb, b_lo, b_hi, A, bk_res2.p, bk_resj.p, ovf, g_part.p);
+                fold(k_bk_fold<false>);
 #ifdef RP_BK_PROF
-            if (getenv("RP_BK_PROF_PRINT")) {
-                unsigned long long v[8];
-                RP_HIP(hipStreamSynchronize(s));
-                RP_HIP(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_bk_prof), sizeof v));
-                const double nw = (double)(v[4] ? v[4] : 1);
-                fprintf(stderr, "[rp] k_bk_fold cycles per workgroup (%llu): records %.0f dup-heads %.0f rows+map %.0f dups+count %.0f\n",
-                        v[4], v[0] / nw, v[1] / nw, v[2] / nw, v[3] / nw);
-                memset(v, 0, sizeof v);
-                RP_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_bk_prof), v, sizeof v));
-                // per-workgroup timeline (the grid's quantization): starts and ends in us
-                // from the first start; how many workgroups run at each tenth of the span
-                std::vector<unsigned long long> wg(2 * kBkMaxBuckets);
-                RP_HIP(hipMemcpyFromSymbol(wg.data(), HIP_SYMBOL(g_bk_wg), sizeof(unsigned long long) * 2 * nb));
-                unsigned long long t0 = ~0ull, t1 = 0;
-                std::vector<double> st(nb), du(nb);
-                for (uint32_t i = 0; i < nb; i++) {
-                    t0 = std::min(t0, wg[2 * i]);
-                    t1 = std::max(t1, wg[2 * i + 1]);
-                }
-                for (uint32_t i = 0; i < nb; i++) {
-                    st[i] = (wg[2 * i] - t0) / 100.0;
-                    du[i] = (wg[2 * i + 1] - wg[2 * i]) / 100.0;
-                }
-                std::vector<double> ss = st, dd = du;
-                std::sort(ss.begin(), ss.end());
-                std::sort(dd.begin(), dd.end());
-                const double span = (t1 - t0) / 100.0;
-                fprintf(stderr, "[rp] k_bk_fold workgroups %u: span %.1f us; starts p50 %.1f p75 %.1f p90 %.1f last %.1f; "
-                                "durations min %.1f p50 %.1f p90 %.1f max %.1f; running at tenths:",
-                        nb, span, ss[nb / 2], ss[nb * 3 / 4], ss[nb * 9 / 10], ss[nb - 1], dd[0], dd[nb / 2], dd[nb * 9 / 10],
-                        dd[nb - 1]);
-                for (int q = 0; q < 10; q++) {
-                    const double t = span * (q + 0.5) / 10.0;
-                    int c = 0;
-                    for (uint32_t i = 0; i < nb; i++) c += (st[i] <= t && st[i] + du[i] > t) ? 1 : 0;
-                    fprintf(stderr, " %d", c);
-                }
-                fprintf(stderr, "\n");
-            }
+            if (knobs.prof_print) bk_prof_print(p.nb, s);
 #endif
-            if (applied && !direct) {
-                const bool v4 = ((uintptr_t)ids & 15) == 0 && ((uintptr_t)applied & 3) == 0;
-                if (v4)
-                    hipLaunchKernelGGL(k_bk_gather<4>, dim3(grid_for((k + 3) / 4, 256, 1u << 30)), dim3(256), 0, s,
-                                       ids, bk_res2.p, bk_resj.p, k, applied);
+            if (applied && p.gather) {
+                if (((uintptr_t)ids & 15) == 0 && ((uintptr_t)applied & 3) == 0)
+                    gather(k_bk_gather<4>, (k + 3) / 4);
                 else
-                    hipLaunchKernelGGL(k_bk_gather<1>, dim3(grid_for(k, 256, 1u << 30)), dim3(256), 0, s, ids,
-                                       bk_res2.p, bk_resj.p, k, applied);
+                    gather(k_bk_gather<1>, k);
             }
-            RP_HIP(hipGetLastError());
-            if (build && nt.size()) {
-                const OvfArgs ov{ids, k, ovf, A, g_part.p, nb, n_applied_out};
-                checksum_dev(s, napplied.p, true, &ov);
-                return;
-            }
-            hipLaunchKernelGGL(k_fold_ovf, dim3(1), dim3(1024), 0, s, ids, k, ovf, A, g_part.p, nb, n_applied_out);
-        } else if (grouped_fold) {
+        } else if (p.path == FoldPath::Grouped) {
             g_slots.reserve((uint64_t)cap * kSlots);
             g_rk.reserve(k);
-            const unsigned g1 = (unsigned)((k + 255) / 256);
+            const unsigned g1 = p.nparts;
             g_part.reserve(g1 + 1);
-            if (fuse_fold(g1, s)) {
+            if (p.fuse && fuse_fits(g1)) {
                 hipLaunchKernelGGL(k_link_fold, dim3(g1), dim3(256), 0, s, ids, k, g_slots.p, g_rk.p, ovf, napplied.p, A,
                                    g_part.p, ws.err.p);
             } else {
@@ -1586,42 +1558,44 @@ struct Members {
                     hipLaunchKernelGGL(k_fold_fast, dim3(g1), dim3(256), 0, s, ids, k, g_rk.p, g_slots.p, A, g_part.p);
                 }
             }
-            RP_HIP(hipGetLastError());
-            if (build && nt.size()) {  // the overflow fold rides on the string build's length launch
-                const OvfArgs ov{ids, k, ovf, A, g_part.p, g1, n_applied_out};
-                checksum_dev(s, napplied.p, true, &ov);
-                return;
-            }
-            hipLaunchKernelGGL(k_fold_ovf, dim3(1), dim3(1024), 0, s, ids, k, ovf, A, g_part.p, g1, n_applied_out);
         } else {
+            sk.reserve(k);
+            sv.reserve(k);
+            uint32_t* done = napplied.p + 2;
             RP_HIP(hipMemsetAsync(napplied.p, 0, sizeof(uint32_t), s));
-            radix_sort_index(ids, sk.p, sv.p, k, 0, bits, s, ws);
-            hipLaunchKernelGGL(k_fold, dim3(g), dim3(256), 0, s, sk.p, sv.p, k, A, nullptr, done + 1, n_applied_out,
-                               nullptr, 0u);
+            radix_sort_index(ids, sk.p, sv.p, k, 0, p.bits, s, ws);
+            hipLaunchKernelGGL(k_fold, dim3(grid_for(k, 256)), dim3(256), 0, s, sk.p, sv.p, k, A, nullptr, done + 1,
+                               n_applied_out, nullptr, 0u);
         }
         RP_HIP(hipGetLastError());
-        if (build) checksum_dev(s, napplied.p, true);
+        // The tail. The bucket and grouped folds leave the overflow step: the string build's length
+        // launch carries it when this batch builds a string, else k_fold_ovf. The sorted fold has
+        // none, and its string is built inline.
+        const bool ovf_step = p.path != FoldPath::Sorted;
+        const bool carried = ovf_step && build && nt.size();
+        const OvfArgs ov{ids, k, ovf, A, g_part.p, p.nparts, n_applied_out};
+        if (ovf_step && !carried) {
+            hipLaunchKernelGGL(k_fold_ovf, dim3(1), dim3(1024), 0, s, ids, k, ovf, A, g_part.p, p.nparts, n_applied_out);
+            RP_HIP(hipGetLastError());
+        }
+        if (build) checksum_dev(s, napplied.p, true, carried ? &ov : nullptr);
     }
 
     // Membership.set over a stash of k changes (arrival order): merge, set, checksum once.
     void set_dev(const uint32_t* ids, const uint8_t* chs, const int64_t* chi, uint32_t k, uint32_t* pick,
                  uint32_t* npick, hipStream_t s) {
+        refresh_knobs();
         if (s != st) RP_HIP(hipStreamSynchronize(st));
         if (!k) {
             if (npick) RP_HIP(hipMemsetAsync(npick, 0, sizeof(uint32_t), s));
             return;
         }
-        if (!ws.err.p) {
-            ws.err.reserve(1);
-            RP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(uint32_t), s));
-        }
+        ensure_err(s);
         sk.reserve(k);
         sv.reserve(k);
         mk.reserve(k);
         mpos.reserve(k + 1);
-        int bits = 8;
-        while (bits < 32 && (1ull << bits) < nt.size()) bits += 8;
-        radix_sort_index(ids, sk.p, sv.p, k, 0, bits, s, ws);
+        radix_sort_index(ids, sk.p, sv.p, k, 0, sort_bits(nt.size()), s, ws);
         RP_HIP(hipMemsetAsync(mk.p, 0, 4ull * k, s));
         hipLaunchKernelGGL(k_merge_pick, dim3(grid_for(k, 256)), dim3(256), 0, s, sk.p, sv.p, k, chi, local_id, mk.p);
         hipLaunchKernelGGL(k_flag_nonzero, dim3(grid_for(k, 256)), dim3(256), 0, s, mk.p, k, mpos.p);
@@ -1668,10 +1642,6 @@ struct Members {
         hipStream_t st = nullptr;
         MckArgs a{};
     } pw;
-    int string_mode() const {
-        const char* e = getenv("RP_MEMBERS_SIDE_BUILD");
-        return e && (*e == '0' || *e == '1') ? *e - '0' : 2;
-    }
     // write a deferred string now (its own launch, on the stream it was deferred on)
     void drain_write() {
         if (!pw.on) return;
@@ -1695,12 +1665,8 @@ struct Members {
         drain_write();
         ck_len.reserve(n + 1);
         ck_pos.reserve(n + 1);
-        const int mode = ov ? string_mode() : 0;
-        if (mode == 1 && !bs) {
-            RP_HIP(hipStreamCreateWithFlags(&bs, hipStreamNonBlocking));
-            RP_HIP(hipEventCreateWithFlags(&ev_len, hipEventDisableTiming));
-            for (auto& e : ev_snap) RP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
+        const int mode = string_mode(knobs, ov != nullptr);
+        if (mode == 1) ensure_build_stream();
         const hipStream_t bst = mode == 1 ? bs : s;  // where this string is written
         // worst-case string: names + ';' + "suspect" + 20 digits per member
         const uint64_t need = (nt.h_bytes.size() + (uint64_t)n * 29 + 16 + 255) & ~255ull;
@@ -1708,26 +1674,17 @@ struct Members {
             flush_checksums();
             RP_HIP(hipStreamSynchronize(pend_st));
         }
-        if (!ck_st) {
-            RP_HIP(hipStreamCreateWithFlags(&ck_st, hipStreamNonBlocking));
-            RP_HIP(hipEventCreateWithFlags(&ev_built, hipEventDisableTiming));
-            for (auto& e : ev_hashed) RP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        }
+        ensure_chain_stream();
         if (need > slot_bytes) {
             RP_HIP(hipStreamSynchronize(ck_st));  // no chain still reads the old pool
             if (bs) RP_HIP(hipStreamSynchronize(bs));  // no writer still writes it
             for (auto& b : group_busy) b = false;
             cur_group = 0;
             ck_buf.release();
-            // 6 GiB of HBM: at C3's 4.7 MB slots, 2 groups of 512 (round 6: the packed chain kernel
-            // hashes 16 to 512 strings in the same ~4 ms, so a group of 512 costs what one of 128
-            // did: 0.0384 -> 0.0311 ms per C3 batch, profiles/r06/r06j/); rounds 2-5 kept 2 GiB and
-            // groups of 128 (1 GiB / 2 groups: 51.4 against 45.2 us per batch, profiles/r04/r04e/)
-            const uint64_t budget = env_pos("RP_MEMBERS_CK_BYTES", 6ull << 30);
-            nslots = (uint32_t)std::min<uint64_t>(kMaxSlots, std::max<uint64_t>(1, budget / need));
-            const uint32_t gmax = (uint32_t)env_pos("RP_MEMBERS_GROUP_SLOTS", kGroupSlots);  // A/B: chains per launch
-            group_slots = std::max<uint32_t>(1, std::min<uint32_t>(gmax, nslots / 2));
-            ngroups = std::max<uint32_t>(1, std::min<uint32_t>(kMaxGroups, nslots / group_slots));
+            const CkPool pool = ck_pool(need, knobs);
+            nslots = pool.nslots;
+            group_slots = pool.group_slots;
+            ngroups = pool.ngroups;
             ck_buf.reserve(need * (uint64_t)group_slots * ngroups);
             slot_bytes = need;
         }
@@ -1740,60 +1697,51 @@ struct Members {
         pend_main = s;
         ck_meta.reserve(4 * kMaxSlots);
         uint8_t* buf = ck_buf.p + slot_bytes * slot_index(npending);
-        {
-            const uint32_t ntl = (n + 255) / 256;
-            uint32_t* meta = ck_meta.p + 4ull * slot_index(npending);
-            if (ov) {
-                if (!ws.err.p) {
-                    ws.err.reserve(1);
-                    RP_HIP(hipMemsetAsync(ws.err.p, 0, sizeof(uint32_t), s));
-                }
-                uint64_t* snap = nullptr;
-                uint32_t* tiles = nullptr;
-                uint32_t* gcopy = nullptr;
-                const uint32_t p = mode == 1 ? snap_p : 0u;
-                if (mode >= 1) {
-                    if (mode == 1 && snap_busy[p]) RP_HIP(hipStreamWaitEvent(s, ev_snap[p], 0));  // its writer has read it
-                    if (snap_rows[p].cap < n) {
-                        if (bs) RP_HIP(hipStreamSynchronize(bs));
-                        snap_rows[p].reserve(n);
-                    }
-                    snap_tiles[p].reserve(ntl);
-                    snap_gate.reserve(2);
-                    snap = snap_rows[p].p;
-                    tiles = snap_tiles[p].p;
-                    gcopy = snap_gate.p + p;
-                } else {
-                    ck_tiles.reserve(ntl);
-                    tiles = ck_tiles.p;
-                }
-                hipLaunchKernelGGL(k_ovf_len, dim3(ntl), dim3(256), 0, s, nt.sorted.p, n, nt.soff.p, tiles,
-                                   ov->ids, ov->k, ov->ovf, ov->A, ov->part, ov->nparts, ov->out,
-                                   napplied.p + 2 + 2, ws.err.p, snap, gcopy);
-                const MckArgs ma{nt.sorted.p, n, rows.p, nt.sbytes.p, nt.soff.p, mode >= 1 ? gcopy : gate, tiles, buf,
-                                 meta, snap};
-                if (mode == 2) {
-                    pw.on = true;
-                    pw.ntl = ntl;
-                    pw.st = s;
-                    pw.a = ma;
-                } else if (mode == 1) {
-                    RP_HIP(hipEventRecord(ev_len, s));
-                    RP_HIP(hipStreamWaitEvent(bs, ev_len, 0));
-                    hipLaunchKernelGGL(k_mck_write, dim3(ntl), dim3(256), 0, bs, ma);
-                    RP_HIP(hipEventRecord(ev_snap[p], bs));
-                    snap_busy[p] = true;
-                    snap_p ^= 1u;
-                } else {
-                    hipLaunchKernelGGL(k_mck_write, dim3(ntl), dim3(256), 0, s, ma);
-                }
-            } else {
-                ck_tiles.reserve(ntl);
-                hipLaunchKernelGGL(k_mck_len, dim3(ntl), dim3(256), 0, s, nt.sorted.p, n, rows.p, nt.soff.p,
-                                   ck_tiles.p);
-                const MckArgs ma{nt.sorted.p, n, rows.p, nt.sbytes.p, nt.soff.p, gate, ck_tiles.p, buf, meta, nullptr};
-                hipLaunchKernelGGL(k_mck_write, dim3(ntl), dim3(256), 0, s, ma);
+        uint32_t* meta = ck_meta.p + 4ull * slot_index(npending);
+        const uint32_t ntl = (n + 255) / 256;
+        if (ov) ensure_err(s);
+        // The tile lengths. Modes 1 and 2 write the string later, from a snapshot of the rows and of
+        // the gate that the length launch takes: mode 1 from one of two, mode 2 from the first.
+        const uint32_t p = mode == 1 ? snap_p : 0u;
+        uint64_t* snap = nullptr;
+        uint32_t* gcopy = nullptr;
+        uint32_t* tiles = nullptr;
+        if (mode >= 1) {
+            if (mode == 1 && snap_busy[p]) RP_HIP(hipStreamWaitEvent(s, ev_snap[p], 0));  // its writer has read it
+            if (snap_rows[p].cap < n) {
+                if (bs) RP_HIP(hipStreamSynchronize(bs));
+                snap_rows[p].reserve(n);
             }
+            snap_tiles[p].reserve(ntl);
+            snap_gate.reserve(2);
+            snap = snap_rows[p].p;
+            tiles = snap_tiles[p].p;
+            gcopy = snap_gate.p + p;
+        } else {
+            ck_tiles.reserve(ntl);
+            tiles = ck_tiles.p;
+        }
+        if (ov)
+            hipLaunchKernelGGL(k_ovf_len, dim3(ntl), dim3(256), 0, s, nt.sorted.p, n, nt.soff.p, tiles, ov->ids, ov->k,
+                               ov->ovf, ov->A, ov->part, ov->nparts, ov->out, napplied.p + 2 + 2, ws.err.p, snap, gcopy);
+        else
+            hipLaunchKernelGGL(k_mck_len, dim3(ntl), dim3(256), 0, s, nt.sorted.p, n, rows.p, nt.soff.p, tiles);
+        // The string: deferred to the next batch's fold launch, on the build stream, or here.
+        const MckArgs ma{nt.sorted.p, n, rows.p, nt.sbytes.p, nt.soff.p, mode >= 1 ? gcopy : gate, tiles, buf, meta, snap};
+        if (mode == 2) {
+            pw.on = true;
+            pw.ntl = ntl;
+            pw.st = s;
+            pw.a = ma;
+        } else if (mode == 1) {
+            RP_HIP(hipEventRecord(ev_len, s));
+            RP_HIP(hipStreamWaitEvent(bs, ev_len, 0));
+            hipLaunchKernelGGL(k_mck_write, dim3(ntl), dim3(256), 0, bs, ma);
+            RP_HIP(hipEventRecord(ev_snap[p], bs));
+            snap_busy[p] = true;
+            snap_p ^= 1u;
+        } else {
+            hipLaunchKernelGGL(k_mck_write, dim3(ntl), dim3(256), 0, s, ma);
         }
         RP_HIP(hipGetLastError());
         if (is_batch && hist_cap) pend_mask.w[npending >> 6] |= 1ull << (npending & 63);
@@ -1811,8 +1759,7 @@ struct Members {
         hash_long_multi(ck_buf.p + slot_bytes * first, slot_bytes, npending, ck_meta.p + 4 * first, ck_st);
         hipLaunchKernelGGL(k_ck_commit, dim3(1), dim3(1), 0, ck_st, ck_meta.p + 4 * first, npending, ck.p);
         RP_HIP(hipGetLastError());
-        uint32_t nb = 0;
-        for (uint64_t w : pend_mask.w) nb += (uint32_t)__builtin_popcountll(w);
+        const uint32_t nb = pending_history();
         // update_dev refuses a batch the history cannot take before it launches anything, so the
         // nb entries always fit here and this path never throws with the group half-flushed
         if (nb) {
@@ -1832,6 +1779,18 @@ struct Members {
         flush_checksums();
         if (ck_st) RP_HIP(hipStreamSynchronize(ck_st));
         for (auto& b : group_busy) b = false;
+    }
+    void ensure_build_stream() {  // mode 1's stream and events, when first used
+        if (bs) return;
+        RP_HIP(hipStreamCreateWithFlags(&bs, hipStreamNonBlocking));
+        RP_HIP(hipEventCreateWithFlags(&ev_len, hipEventDisableTiming));
+        for (auto& e : ev_snap) RP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    void ensure_chain_stream() {  // the chains' side stream and events, at the first string
+        if (ck_st) return;
+        RP_HIP(hipStreamCreateWithFlags(&ck_st, hipStreamNonBlocking));
+        RP_HIP(hipEventCreateWithFlags(&ev_built, hipEventDisableTiming));
+        for (auto& e : ev_hashed) RP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     void release_streams() {
         if (bs) {
@@ -2126,6 +2085,7 @@ int rp_members_checksum_history_drain(rp_members* h, uint32_t count) {
 int rp_members_compute_checksum(rp_members* h) {
     return guard([&] {
         rp::Members& m = MB(h);
+        m.refresh_knobs();
         m.checksum_dev(m.st, nullptr);
         m.settle_checksums();
     });
@@ -2138,6 +2098,7 @@ int rp_members_checksum_string(rp_members* h, char* buf, uint64_t cap, uint64_t*
         uint32_t total = 0;
         const uint8_t* str = nullptr;
         if (n) {
+            m.refresh_knobs();
             m.checksum_dev(m.st, nullptr);
             str = m.ck_buf.p + m.slot_bytes * m.slot_index(m.npending - 1);
             RP_HIP(hipMemcpyAsync(&total, m.ck_meta.p + 4ull * m.slot_index(m.npending - 1), 4,

@@ -35,8 +35,9 @@ def u64(a):
 
 @pytest.fixture(params=PATHS)
 def make(request, gpu, monkeypatch):
-    """A handle factory for the fold path of this parameter (the environment is read when the
-    handle is created and at every batch, so it is set first and stays for the test)."""
+    """A handle factory for the fold path of this parameter (every knob is read when the handle is
+    created and again at the top of every update, set and checksum call, MemberKnobs of
+    csrc/rp_members_plan.h; it is set first and stays for the test)."""
     for v in ("RP_MEMBERS_SORTED_FOLD", "RP_MEMBERS_BUCKET_FOLD", "RP_MEMBERS_FUSE"):
         monkeypatch.delenv(v, raising=False)
     if request.param == "sorted":

@@ -294,6 +294,62 @@ def test_deferred_string_write_across_paths(gpu, orc, monkeypatch):
     m.close()
 
 
+def test_fold_path_chosen_per_batch(gpu, orc, monkeypatch):
+    """One handle whose batches take, in turn, the grouped fold, the sorted fold, the grouped fold,
+    the bucket fold, the sorted fold and the grouped fold (RP_MEMBERS_SORTED_FOLD and
+    RP_MEMBERS_BUCKET_FOLD are read at every batch). The first two batches hold an address with
+    17 changes: one more than the grouped fold's slots, so the first takes the overflow fold, and
+    the sorted batch after it finds the per-address counters the grouped fold left and must leave
+    them clean for the grouped batch that follows. After every batch the applied flags and the
+    applied count against the oracle's; every batch's checksum from the per-batch history."""
+    S = synth()
+    n, k = 3000, 2000
+    names, st0, inc0 = S.c3_members(n)
+    m = gpu.Membership(whoami=names[0], capacity=n)
+    m.checksum_shard(1, 0, history_cap=16)
+    o = orc.Members(names, local=names[0], join_seed=0)
+    ids0 = np.asarray(m.intern(names), dtype=np.uint32)
+    m.update_ids(ids0, st0, inc0, now_ms=1)
+    o.update_ids(ids0, st0, inc0, False, 1)
+    want = [o.checksum]
+    stream = torch.cuda.current_stream().cuda_stream
+    na = torch.zeros(1, dtype=torch.int32, device="cuda")
+    rng = np.random.default_rng(6)
+    plan = [("grouped", 17), ("sorted", 17), ("grouped", 0), ("bucket", 0), ("sorted", 0), ("grouped", 0)]
+    keep = []
+    for b, (what, hot) in enumerate(plan):
+        for e in ("RP_MEMBERS_BUCKET_FOLD", "RP_MEMBERS_SORTED_FOLD"):
+            monkeypatch.delenv(e, raising=False)
+        if what == "bucket":
+            monkeypatch.setenv("RP_MEMBERS_BUCKET_FOLD", "1")
+        if what == "sorted":
+            monkeypatch.setenv("RP_MEMBERS_SORTED_FOLD", "1")
+        ids, us, ui = (list(x) for x in S.c3_updates(n, k - hot, seed=700 + b, base_inc=inc0 + 3 * b))
+        for _ in range(hot):  # the hot address, 40 + b, at random places of the batch
+            p = int(rng.integers(0, len(ids) + 1))
+            ids.insert(p, 40 + b)
+            us.insert(p, int(rng.integers(0, 4)))
+            ui.insert(p, int(inc0[40 + b]) + 3 * b + int(rng.integers(-2, 3)))
+        ids, us, ui = np.asarray(ids, np.uint32), np.asarray(us, np.uint8), np.asarray(ui, np.int64)
+        assert len(ids) == k and (hot == 0 or int((ids == 40 + b).sum()) >= hot)
+        d = [torch.from_numpy(ids.view(np.int32)).cuda(), torch.from_numpy(us).cuda(), torch.from_numpy(ui).cuda()]
+        app = torch.full((k,), 9, dtype=torch.uint8, device="cuda")
+        keep.append((d, app))
+        m.update_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), k, 1434500000000 + b, app.data_ptr(),
+                     None, None, na.data_ptr(), stream)
+        oa, _, _, ona = o.update_ids(ids, us, ui, False, 1434500000000 + b)
+        want.append(o.checksum)
+        assert int(na.item()) == ona, (b, what)
+        assert np.array_equal(app.cpu().numpy() > 0, np.asarray(oa) > 0), (b, what)
+    for e in ("RP_MEMBERS_BUCKET_FOLD", "RP_MEMBERS_SORTED_FOLD"):
+        monkeypatch.delenv(e, raising=False)
+    h, a = m.checksum_history()
+    assert len(h) == len(want) and a.all()  # (every batch here applies something)
+    assert h.tolist() == want  # entry b + 1 is batch b's
+    assert m.checksum == want[-1]
+    m.close()
+
+
 @pytest.mark.parametrize("budget", [None, "3"], ids=["default-pool", "three-slots"])
 def test_checksum_groups_wrap_with_reads(gpu, orc, budget, monkeypatch):
     """300 unread batches cycle through every slot group more than once (a group is rebuilt only
