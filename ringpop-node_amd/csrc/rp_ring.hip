@@ -1854,6 +1854,31 @@ __global__ __launch_bounds__(256) void k_lookupn_fix(const uint8_t* __restrict__
     }
 }
 
+// Key k's hash as every pass over a key stream takes it: the caller's hash, else the bytes at
+// k * stride, else the bytes at off[k] .. off[k + 1].
+__device__ __forceinline__ uint32_t key_hash(const uint8_t* __restrict__ keys, const uint64_t* __restrict__ off,
+                                             uint32_t stride, const uint32_t* __restrict__ hashes, uint64_t k) {
+    if (hashes) return hashes[k];
+    uint64_t b, e;
+    if (stride) {
+        b = k * stride;
+        e = b + stride;
+    } else {
+        b = off[k];
+        e = off[k + 1];
+    }
+    return fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
+}
+
+// The hash of a 36-byte key from its nine dwords: in LDS (a staged tile's, k_moved / k_handoff) or
+// in global memory at a 4-byte aligned address (k_route).
+__device__ __forceinline__ uint32_t key_hash36(const uint32_t* src) {
+    uint32_t w[9];
+#pragma unroll
+    for (int j = 0; j < 9; j++) w[j] = src[j];
+    return fh::hash32_words<36>(w);
+}
+
 // Generic keys: per-thread byte fetches (variable length via uint64 offsets, or any stride),
 // or precomputed hashes (hashes != null).
 template <int MAXN, class View>
@@ -1866,21 +1891,7 @@ __global__ __launch_bounds__(kLkThreads) void k_lookupn_generic(const uint8_t* _
                                                                 uint8_t* __restrict__ counts) {
     const uint64_t gstride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gstride) {
-        uint32_t h;
-        if (hashes) {
-            h = hashes[k];
-        } else {
-            uint64_t b, e;
-            if (stride) {
-                b = k * stride;
-                e = b + stride;
-            } else {
-                b = off[k];
-                e = off[k + 1];
-            }
-            h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
-        }
-        const uint32_t i = rv.find(h);
+        const uint32_t i = rv.find(key_hash(keys, off, stride, hashes, k));
         uint32_t* row = out + k * W;
         int c;
         if constexpr (MAXN > 0) {
@@ -3121,6 +3132,22 @@ static void with_need(int need, F&& f) {
     }
 }
 
+// A key stream on the device, as the kernels take it: key bytes (stride > 0: key i is
+// keys[i * stride .. + stride), else keys[off[i] .. off[i + 1])) or, with `hashes`, the key hashes.
+struct DevKeys {
+    const uint8_t* keys;
+    const uint64_t* off;
+    uint32_t stride;
+    const uint32_t* hashes;
+    // 36-byte keys at a 4-byte aligned address: what the kernels' fixed forms read as nine dwords
+    bool fixed36() const { return !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0); }
+    // the stream from key k0 on (a chunk of a pass); the buffers the form does not read are null
+    DevKeys from(uint64_t k0) const {
+        return {hashes ? nullptr : (stride ? keys + k0 * stride : keys), (!hashes && !stride) ? off + k0 : nullptr, stride,
+                hashes ? hashes + k0 : nullptr};
+    }
+};
+
 // The kernels over any view: 36-byte keys at a 4-byte-aligned address in registers
 // (k_lookupn_fixed), every other key form and caller hashes per thread (k_lookupn_generic).
 // `ablate`: LookupKnobs::ablate.
@@ -3128,7 +3155,7 @@ template <class View>
 static void launch_lookupn_view(const View& rv, const uint8_t* keys, const uint64_t* off, uint32_t stride,
                                 const uint32_t* hashes, uint64_t n, int np, uint32_t W, uint32_t* out,
                                 uint8_t* counts, hipStream_t st, int ablate) {
-    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
+    const bool fixed36 = DevKeys{keys, off, stride, hashes}.fixed36();
     const int need = np <= 0 ? 1 : np;
     const auto fixed = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(grid_for(n, kLkThreads, 256 * 8)), dim3(kLkThreads), 0, st, keys, n, rv, np, W,
@@ -3450,7 +3477,7 @@ static void launch_lookupn(Ring& r, const uint8_t* keys, const uint64_t* off, ui
     // the ring is rebuilt on r.st; make the caller's stream wait for it
     if (st != r.st) RP_HIP(hipStreamSynchronize(r.st));
     const LookupKnobs k = lookup_knobs();
-    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
+    const bool fixed36 = DevKeys{keys, off, stride, hashes}.fixed36();
     const int need = np <= 0 ? 1 : np;
     const bool use_packed = r.packed && !k.wide;
     const bool use_compact = r.compact && !k.layout_packed && !k.wide;
@@ -3682,11 +3709,74 @@ __device__ __forceinline__ void moved_walk(const RingView& rv, uint32_t i, int n
     }
 }
 
-// FIXED: 36-byte keys at stride 36 from a 4-byte aligned base; full tiles of a 16-byte aligned
-// base stream through LDS with non-temporal 16-B loads (read once; they must not evict the two
-// rings' tables from L2). Otherwise: per-thread byte fetches (offsets, any stride, any base) or
-// precomputed hashes. One tile of 256 * KPL keys per workgroup, key q * 256 + tid of the tile in
-// slot q of thread tid, so that (q, wave, lane) order is key order.
+// The tile passes' shared pieces (k_moved, k_handoff). One tile of TILE = 256 * KPL keys per
+// workgroup, tile = ticket.
+//
+// stage_tile36: the tile's `cnt` 36-byte keys from keys + base * 36 (a 4-byte aligned base) into
+// sk[TILE * 9]: full tiles of a 16-byte aligned base with non-temporal 16-B loads (read once; they
+// must not evict the two rings' tables from L2), every other tile dword by dword. Syncs.
+template <int TILE>
+__device__ __forceinline__ void stage_tile36(uint32_t* sk, const uint8_t* __restrict__ keys, uint32_t base,
+                                             uint32_t cnt, int tid) {
+    constexpr int W4 = 9;                    // dwords per 36-byte key
+    constexpr int V4 = TILE * W4 / 4;        // 16-B vectors per full tile
+    constexpr int PER = (V4 + kLkThreads - 1) / kLkThreads;
+    static_assert((TILE * W4) % 4 == 0, "tile must be a whole number of 16-B vectors");
+    const uint8_t* src = keys + (uint64_t)base * 36u;
+    if (cnt == (uint32_t)TILE && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
+        const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+        u32x4* d4 = reinterpret_cast<u32x4*>(sk);
+        u32x4 pre[PER];
+#pragma unroll
+        for (int q = 0; q < PER; q++) {
+            const int k = tid + q * kLkThreads;
+            if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
+        }
+#pragma unroll
+        for (int q = 0; q < PER; q++) {
+            const int k = tid + q * kLkThreads;
+            if (k < V4) d4[k] = pre[q];
+        }
+    } else {
+        const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
+        for (uint32_t k = tid; k < cnt * W4; k += kLkThreads) sk[k] = s1[k];
+    }
+    __syncthreads();
+}
+
+// tile_offset: the order-preserving compaction's tail. Every wave's lane 0 has stored its record
+// count of slot q in s_cnt[q * 4 + wave]; this gives pre[q], the records of the tile before the
+// caller's (slot q, wave) segment, publishes the tile's total, returns the records of all earlier
+// tiles (decoupled look-back) and has the last tile write *count. Syncs before and after.
+template <int KPL>
+__device__ __forceinline__ uint32_t tile_offset(const uint32_t* s_cnt, uint32_t* s_excl, uint64_t* __restrict__ lb,
+                                                uint32_t tile, uint64_t tag, uint32_t ntiles,
+                                                uint32_t* __restrict__ count, uint32_t* err, uint32_t (&pre)[KPL]) {
+    const int tid = threadIdx.x, wave = tid >> 6;
+    __syncthreads();
+    uint32_t total = 0;
+#pragma unroll
+    for (int s = 0; s < KPL * (kLkThreads / 64); s++) {
+        if ((s & (kLkThreads / 64 - 1)) == wave) pre[s / (kLkThreads / 64)] = total;
+        total += s_cnt[s];
+    }
+    if (tid == 0) lb_store(lb + tile, tag | (tile == 0 ? kLbP : kLbA) | total);
+    if (tid < 64) {
+        const uint32_t excl = lookback_wave(lb, tile, tag, err);
+        if (tid == 0) {
+            if (tile > 0) lb_store(lb + tile, tag | kLbP | (excl + total));
+            *s_excl = excl;
+            if (tile == ntiles - 1) *count = excl + total;
+        }
+    }
+    __syncthreads();
+    return *s_excl;
+}
+
+// FIXED: 36-byte keys at stride 36 from a 4-byte aligned base, staged through LDS (stage_tile36).
+// Otherwise: per-thread byte fetches (offsets, any stride, any base) or precomputed hashes
+// (key_hash). Key q * 256 + tid of the tile in slot q of thread tid, so that (q, wave, lane) order
+// is key order.
 template <int MAXN, int KPL, bool FIXED>
 __global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict__ keys,
                                                       const uint64_t* __restrict__ off, uint32_t stride,
@@ -3697,11 +3787,7 @@ __global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict_
                                                       uint64_t* __restrict__ lb, unsigned long long* ctr,
                                                       uint64_t tag, uint32_t ntiles, uint32_t* err) {
     constexpr int TILE = kLkThreads * KPL;
-    constexpr int W4 = 9;                    // dwords per 36-byte key
-    constexpr int V4 = TILE * W4 / 4;        // 16-B vectors per full tile
-    constexpr int PER = (V4 + kLkThreads - 1) / kLkThreads;
-    static_assert((TILE * W4) % 4 == 0, "tile must be a whole number of 16-B vectors");
-    __shared__ __attribute__((aligned(16))) uint32_t sk[FIXED ? TILE * W4 : 4];
+    __shared__ __attribute__((aligned(16))) uint32_t sk[FIXED ? TILE * 9 : 4];
     __shared__ uint32_t s_cnt[KPL * (kLkThreads / 64)];
     __shared__ uint32_t s_excl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -3709,28 +3795,7 @@ __global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict_
     if (tile >= ntiles) return;  // a ticket count out of step (reported): never write out of bounds
     const uint32_t base = tile * (uint32_t)TILE;
     const uint32_t cnt = n - base < (uint32_t)TILE ? n - base : (uint32_t)TILE;
-    if constexpr (FIXED) {
-        const uint8_t* src = keys + (uint64_t)base * 36u;
-        if (cnt == (uint32_t)TILE && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
-            const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
-            u32x4* d4 = reinterpret_cast<u32x4*>(sk);
-            u32x4 pre[PER];
-#pragma unroll
-            for (int q = 0; q < PER; q++) {
-                const int k = tid + q * kLkThreads;
-                if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
-            }
-#pragma unroll
-            for (int q = 0; q < PER; q++) {
-                const int k = tid + q * kLkThreads;
-                if (k < V4) d4[k] = pre[q];
-            }
-        } else {
-            const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
-            for (uint32_t k = tid; k < cnt * W4; k += kLkThreads) sk[k] = s1[k];
-        }
-        __syncthreads();
-    }
+    if constexpr (FIXED) stage_tile36<TILE>(sk, keys, base, cnt, tid);
     uint32_t rb[KPL][MAXN], ra[KPL][MAXN];
     bool mv[KPL];
 #pragma unroll
@@ -3740,26 +3805,7 @@ __global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict_
 #pragma unroll
         for (int j = 0; j < MAXN; j++) rb[q][j] = ra[q][j] = NIL;
         if (kl < cnt) {
-            uint32_t h;
-            if constexpr (FIXED) {
-                uint32_t w[W4];
-#pragma unroll
-                for (int j = 0; j < W4; j++) w[j] = sk[kl * W4 + j];
-                h = fh::hash32_words<36>(w);
-            } else if (hashes) {
-                h = hashes[base + kl];
-            } else {
-                const uint64_t k = (uint64_t)base + kl;
-                uint64_t b, e;
-                if (stride) {
-                    b = k * stride;
-                    e = b + stride;
-                } else {
-                    b = off[k];
-                    e = off[k + 1];
-                }
-                h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
-            }
+            const uint32_t h = FIXED ? key_hash36(sk + kl * 9) : key_hash(keys, off, stride, hashes, (uint64_t)base + kl);
             moved_walk<MAXN>(bv, moved_find(bv, h), npb, rb[q]);
             moved_walk<MAXN>(av, moved_find(av, h), npa, ra[q]);
             bool d = false;
@@ -3777,24 +3823,8 @@ __global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict_
         rank[q] = (uint32_t)__popcll(m & lt_mask);
         if (lane == 0) s_cnt[q * (kLkThreads / 64) + wave] = (uint32_t)__popcll(m);
     }
-    __syncthreads();
-    uint32_t pre[KPL], total = 0;
-#pragma unroll
-    for (int s = 0; s < KPL * (kLkThreads / 64); s++) {
-        if ((s & (kLkThreads / 64 - 1)) == wave) pre[s / (kLkThreads / 64)] = total;
-        total += s_cnt[s];
-    }
-    if (tid == 0) lb_store(lb + tile, tag | (tile == 0 ? kLbP : kLbA) | total);
-    if (tid < 64) {
-        const uint32_t excl = lookback_wave(lb, tile, tag, err);
-        if (tid == 0) {
-            if (tile > 0) lb_store(lb + tile, tag | kLbP | (excl + total));
-            s_excl = excl;
-            if (tile == ntiles - 1) *count = excl + total;
-        }
-    }
-    __syncthreads();
-    const uint32_t gbase = s_excl;
+    uint32_t pre[KPL];
+    const uint32_t gbase = tile_offset<KPL>(s_cnt, &s_excl, lb, tile, tag, ntiles, count, err, pre);
 #pragma unroll
     for (int q = 0; q < KPL; q++) {
         const uint32_t p = gbase + pre[q] + rank[q];
@@ -3811,19 +3841,33 @@ __global__ __launch_bounds__(kLkThreads) void k_moved(const uint8_t* __restrict_
     }
 }
 
-template <int MAXN, int KPL, bool FIXED, class... A>
-static void launch_moved_k(uint32_t n, hipStream_t st, Scratch& ws, A... args) {
+// A tile pass over n keys: one workgroup a tile of 256 * KPL keys, the look-back state after `args`
+template <int KPL, class Kernel, class... A>
+static void launch_tiles(Kernel kernel, uint32_t n, hipStream_t st, Scratch& ws, A... args) {
     const uint32_t ntiles = (uint32_t)(((uint64_t)n + kLkThreads * KPL - 1) / (kLkThreads * KPL));
     const LookBack L = lookback_prepare(ws, ntiles, st);
-    hipLaunchKernelGGL((k_moved<MAXN, KPL, FIXED>), dim3(ntiles), dim3(kLkThreads), 0, st, args..., L.words, L.ticket,
-                       L.tag, ntiles, L.err);
+    hipLaunchKernelGGL(kernel, dim3(ntiles), dim3(kLkThreads), 0, st, args..., L.words, L.ticket, L.tag, ntiles, L.err);
     RP_HIP(hipGetLastError());
 }
 
+// f(Int<MAXN>{}, Int<KPL>{}, FIXED{}): the tile passes' kernel shape for rows of W slots. Staged
+// 36-byte keys go four a lane (two with rows of eight), every other form one.
+template <class F>
+static void with_tile_shape(uint32_t W, bool fixed36, F&& f) {
+    if (fixed36) {
+        if (W == 1) f(Int<1>{}, Int<4>{}, std::true_type{});
+        else if (W <= 4) f(Int<4>{}, Int<4>{}, std::true_type{});
+        else f(Int<8>{}, Int<2>{}, std::true_type{});
+    } else {
+        if (W == 1) f(Int<1>{}, Int<1>{}, std::false_type{});
+        else if (W <= 4) f(Int<4>{}, Int<1>{}, std::false_type{});
+        else f(Int<8>{}, Int<1>{}, std::false_type{});
+    }
+}
+
 // before / after rows of W slots each; outputs as rp_ring_moved_keys_dev documents
-static void moved_keys(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t* off, uint32_t stride,
-                       const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t cap, uint32_t* idx, uint32_t* brow,
-                       uint32_t* arow, uint32_t* count, hipStream_t st) {
+static void moved_keys(Ring& r, const Snap& s, const DevKeys& k, uint64_t n, int32_t nrep, uint32_t cap, uint32_t* idx,
+                       uint32_t* brow, uint32_t* arow, uint32_t* count, hipStream_t st) {
     RP_REQUIRE(nrep <= 8, "moved_keys: nrep is at most 8 (the rows are compared in registers)");
     RP_REQUIRE(n < (1ull << 32), "moved_keys: at most 2^32-1 keys per call");
     RP_REQUIRE(s.device == r.device, "moved_keys: the snapshot lives on another device");
@@ -3837,21 +3881,11 @@ static void moved_keys(Ring& r, const Snap& s, const uint8_t* keys, const uint64
     }
     const int npb = replicas(nrep, s.server_count).np;
     const auto [npa, W] = replicas(nrep, r.server_count);
-    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const RingView bv = s.view(), av = r.view();
-#define RP_MOVED(MAXN, KPL, FIXED)                                                                                  \
-    launch_moved_k<MAXN, KPL, FIXED>((uint32_t)n, st, r.ws, keys, off, stride, hashes, (uint32_t)n, bv, npb, av, npa, \
-                                     W, cap, idx, brow, arow, count)
-    if (fixed36) {
-        if (W == 1) RP_MOVED(1, 4, true);
-        else if (W <= 4) RP_MOVED(4, 4, true);
-        else RP_MOVED(8, 2, true);
-    } else {
-        if (W == 1) RP_MOVED(1, 1, false);
-        else if (W <= 4) RP_MOVED(4, 1, false);
-        else RP_MOVED(8, 1, false);
-    }
-#undef RP_MOVED
+    with_tile_shape(W, k.fixed36(), [&, npa = npa, W = W](auto maxn, auto kpl, auto fixed) {
+        launch_tiles<kpl()>(k_moved<maxn(), kpl(), fixed()>, (uint32_t)n, st, r.ws, k.keys, k.off, k.stride, k.hashes,
+                            (uint32_t)n, bv, npb, av, npa, W, cap, idx, brow, arow, count);
+    });
 }
 
 // ------------------------------------------------------------- hand-off plan
@@ -3877,11 +3911,7 @@ __global__ __launch_bounds__(kLkThreads) void k_handoff(const uint8_t* __restric
                                                         uint64_t* __restrict__ lb, unsigned long long* ctr,
                                                         uint64_t tag, uint32_t ntiles, uint32_t* err) {
     constexpr int TILE = kLkThreads * KPL;
-    constexpr int W4 = 9;                    // dwords per 36-byte key
-    constexpr int V4 = TILE * W4 / 4;        // 16-B vectors per full tile
-    constexpr int PER = (V4 + kLkThreads - 1) / kLkThreads;
-    static_assert((TILE * W4) % 4 == 0, "tile must be a whole number of 16-B vectors");
-    __shared__ __attribute__((aligned(16))) uint32_t sk[FIXED ? TILE * W4 : 4];
+    __shared__ __attribute__((aligned(16))) uint32_t sk[FIXED ? TILE * 9 : 4];
     __shared__ uint32_t s_cnt[KPL * (kLkThreads / 64)];
     __shared__ uint32_t s_excl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -3889,28 +3919,7 @@ __global__ __launch_bounds__(kLkThreads) void k_handoff(const uint8_t* __restric
     if (tile >= ntiles) return;  // a ticket count out of step (reported): never write out of bounds
     const uint32_t base = tile * (uint32_t)TILE;
     const uint32_t cnt = n - base < (uint32_t)TILE ? n - base : (uint32_t)TILE;
-    if constexpr (FIXED) {  // (k_moved's staging)
-        const uint8_t* src = keys + (uint64_t)base * 36u;
-        if (cnt == (uint32_t)TILE && (reinterpret_cast<uintptr_t>(keys) & 15) == 0) {
-            const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
-            u32x4* d4 = reinterpret_cast<u32x4*>(sk);
-            u32x4 pre[PER];
-#pragma unroll
-            for (int q = 0; q < PER; q++) {
-                const int k = tid + q * kLkThreads;
-                if (k < V4) pre[q] = __builtin_nontemporal_load(s4 + k);
-            }
-#pragma unroll
-            for (int q = 0; q < PER; q++) {
-                const int k = tid + q * kLkThreads;
-                if (k < V4) d4[k] = pre[q];
-            }
-        } else {
-            const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
-            for (uint32_t k = tid; k < cnt * W4; k += kLkThreads) sk[k] = s1[k];
-        }
-        __syncthreads();
-    }
+    if constexpr (FIXED) stage_tile36<TILE>(sk, keys, base, cnt, tid);
     uint32_t ra[KPL][MAXN], gm[KPL], sr[KPL];  // the row now, its gained slots (bit q), the source
 #pragma unroll
     for (int q = 0; q < KPL; q++) {
@@ -3920,26 +3929,7 @@ __global__ __launch_bounds__(kLkThreads) void k_handoff(const uint8_t* __restric
 #pragma unroll
         for (int j = 0; j < MAXN; j++) ra[q][j] = NIL;
         if (kl < cnt) {
-            uint32_t h;
-            if constexpr (FIXED) {
-                uint32_t w[W4];
-#pragma unroll
-                for (int j = 0; j < W4; j++) w[j] = sk[kl * W4 + j];
-                h = fh::hash32_words<36>(w);
-            } else if (hashes) {
-                h = hashes[base + kl];
-            } else {
-                const uint64_t k = (uint64_t)base + kl;
-                uint64_t b, e;
-                if (stride) {
-                    b = k * stride;
-                    e = b + stride;
-                } else {
-                    b = off[k];
-                    e = off[k + 1];
-                }
-                h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
-            }
+            const uint32_t h = FIXED ? key_hash36(sk + kl * 9) : key_hash(keys, off, stride, hashes, (uint64_t)base + kl);
             uint32_t rb[MAXN];
             moved_walk<MAXN>(bv, moved_find(bv, h), npb, rb);
             moved_walk<MAXN>(av, moved_find(av, h), npa, ra[q]);
@@ -3979,24 +3969,8 @@ __global__ __launch_bounds__(kLkThreads) void k_handoff(const uint8_t* __restric
         rank[q] = rk;
         if (lane == 0) s_cnt[q * (kLkThreads / 64) + wave] = tot;
     }
-    __syncthreads();
-    uint32_t pre[KPL], total = 0;
-#pragma unroll
-    for (int s = 0; s < KPL * (kLkThreads / 64); s++) {
-        if ((s & (kLkThreads / 64 - 1)) == wave) pre[s / (kLkThreads / 64)] = total;
-        total += s_cnt[s];
-    }
-    if (tid == 0) lb_store(lb + tile, tag | (tile == 0 ? kLbP : kLbA) | total);
-    if (tid < 64) {
-        const uint32_t excl = lookback_wave(lb, tile, tag, err);
-        if (tid == 0) {
-            if (tile > 0) lb_store(lb + tile, tag | kLbP | (excl + total));
-            s_excl = excl;
-            if (tile == ntiles - 1) *count = excl + total;
-        }
-    }
-    __syncthreads();
-    const uint32_t gbase = s_excl;
+    uint32_t pre[KPL];
+    const uint32_t gbase = tile_offset<KPL>(s_cnt, &s_excl, lb, tile, tag, ntiles, count, err, pre);
 #pragma unroll
     for (int q = 0; q < KPL; q++) {
         uint32_t p = gbase + pre[q] + rank[q];
@@ -4013,15 +3987,6 @@ __global__ __launch_bounds__(kLkThreads) void k_handoff(const uint8_t* __restric
             }
         }
     }
-}
-
-template <int MAXN, int KPL, bool FIXED, class... A>
-static void launch_handoff_k(uint32_t n, hipStream_t st, Scratch& ws, A... args) {
-    const uint32_t ntiles = (uint32_t)(((uint64_t)n + kLkThreads * KPL - 1) / (kLkThreads * KPL));
-    const LookBack L = lookback_prepare(ws, ntiles, st);
-    hipLaunchKernelGGL((k_handoff<MAXN, KPL, FIXED>), dim3(ntiles), dim3(kLkThreads), 0, st, args..., L.words,
-                       L.ticket, L.tag, ntiles, L.err);
-    RP_HIP(hipGetLastError());
 }
 
 // Grouping: the records sorted by dst (stable, so (key, slot) order inside a group). T =
@@ -4071,9 +4036,8 @@ __global__ void k_handoff_emit(const uint32_t* __restrict__ sd, const uint32_t* 
 // documents. known_count: the host forms read the record count back after the first pass and
 // group exactly min(count, cap) records; the device form groups over min(cap, n * W) slots,
 // padded with a key that sorts last.
-static void handoff(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t* off, uint32_t stride,
-                    const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t only_src, uint32_t cap,
-                    uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src, uint8_t* slot,
+static void handoff(Ring& r, const Snap& s, const DevKeys& k, uint64_t n, int32_t nrep, uint32_t only_src,
+                    uint32_t cap, uint32_t* dests, uint32_t* goff, uint32_t* key_idx, uint32_t* src, uint8_t* slot,
                     uint32_t* ndest, uint32_t* count, hipStream_t st, bool known_count) {
     const int npb = replicas(nrep, s.server_count).np;
     const auto [npa, W] = replicas(nrep, r.server_count);
@@ -4104,22 +4068,12 @@ static void handoff(Ring& r, const Snap& s, const uint8_t* keys, const uint64_t*
     const int sort_bits = bits_for(id_bound);
     // the slots past the record count sort last (0xFF..: above every id in the sorted bits)
     if (m && !known_count) RP_HIP(hipMemsetAsync(ws.dst.p, 0xFF, 4ull * m, st));
-    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
     const RingView bv = s.view(), av = r.view();
-#define RP_HANDOFF(MAXN, KPL, FIXED)                                                                                   \
-    launch_handoff_k<MAXN, KPL, FIXED>((uint32_t)n, st, r.ws, keys, off, stride, hashes, (uint32_t)n, bv, npb, av, npa, \
-                                       (const uint8_t*)r.d_inring.p, r.inring_n, only_src, m, ws.key.p, ws.dst.p,       \
-                                       ws.src.p, ws.slot.p, count)
-    if (fixed36) {
-        if (W == 1) RP_HANDOFF(1, 4, true);
-        else if (W <= 4) RP_HANDOFF(4, 4, true);
-        else RP_HANDOFF(8, 2, true);
-    } else {
-        if (W == 1) RP_HANDOFF(1, 1, false);
-        else if (W <= 4) RP_HANDOFF(4, 1, false);
-        else RP_HANDOFF(8, 1, false);
-    }
-#undef RP_HANDOFF
+    with_tile_shape(W, k.fixed36(), [&, npa = npa](auto maxn, auto kpl, auto fixed) {
+        launch_tiles<kpl()>(k_handoff<maxn(), kpl(), fixed()>, (uint32_t)n, st, r.ws, k.keys, k.off, k.stride, k.hashes,
+                            (uint32_t)n, bv, npb, av, npa, (const uint8_t*)r.d_inring.p, r.inring_n, only_src, m,
+                            ws.key.p, ws.dst.p, ws.src.p, ws.slot.p, count);
+    });
     if (m == 0) {  // counts only
         RP_HIP(hipMemsetAsync(ndest, 0, sizeof(uint32_t), st));
         if (goff) RP_HIP(hipMemsetAsync(goff, 0, sizeof(uint32_t), st));
@@ -4308,15 +4262,13 @@ static void owner_load_walk(LoadScratch& ls, uint64_t n, int32_t nrep, uint32_t 
     }
 }
 
-static void owner_load(Ring& r, LoadScratch& ls, const uint8_t* keys, const uint64_t* off, uint32_t stride,
-                       const uint32_t* hashes, uint64_t n, int32_t nrep, uint32_t id_cap, int accumulate,
-                       unsigned long long* load, hipStream_t st) {
+static void owner_load(Ring& r, LoadScratch& ls, const DevKeys& k, uint64_t n, int32_t nrep, uint32_t id_cap,
+                       int accumulate, unsigned long long* load, hipStream_t st) {
     const Replicas rep = replicas(nrep, r.server_count);
     owner_load_walk(ls, n, nrep, r.nt.size(), id_cap, r.M != 0, accumulate, load, r.device, st,
                     [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
-                        launch_lookupn(r, hashes ? nullptr : (stride ? keys + k0 * stride : keys),
-                                       (!hashes && !stride) ? off + k0 : nullptr, stride, hashes ? hashes + k0 : nullptr,
-                                       cnt, rep.np, rep.W, rows, nullptr, st);
+                        const DevKeys c = k.from(k0);
+                        launch_lookupn(r, c.keys, c.off, c.stride, c.hashes, cnt, rep.np, rep.W, rows, nullptr, st);
                     });
 }
 
@@ -4693,26 +4645,8 @@ __global__ __launch_bounds__(kRouteThreads) void k_route(
         uint32_t pos = 0, tk = NIL, o0 = 0;
         if (lane < cnt) {
             const uint64_t k = base + lane;
-            uint32_t h;
-            if constexpr (FIXED) {
-                const uint32_t* s1 = reinterpret_cast<const uint32_t*>(keys + k * 36u);
-                uint32_t kw[9];
-#pragma unroll
-                for (int j = 0; j < 9; j++) kw[j] = s1[j];
-                h = fh::hash32_words<36>(kw);
-            } else if (hashes) {
-                h = hashes[k];
-            } else {
-                uint64_t b, e;
-                if (stride) {
-                    b = k * stride;
-                    e = b + stride;
-                } else {
-                    b = off[k];
-                    e = off[k + 1];
-                }
-                h = fh::hash32(fh::PtrSrc{keys + b}, (uint32_t)(e - b));
-            }
+            const uint32_t h = FIXED ? key_hash36(reinterpret_cast<const uint32_t*>(keys + k * 36u))
+                                     : key_hash(keys, off, stride, hashes, k);
             pos = moved_find(rv, h);
             if (pos >= M) pos = 0;
             o0 = rv.own[pos];
@@ -4794,16 +4728,15 @@ __global__ __launch_bounds__(kRouteThreads) void k_route(
 }
 
 // Outputs as rp_ring_route_views_dev documents; everything is queued on st.
-static void route_views(Ring& r, const uint8_t* keys, const uint64_t* off, uint32_t stride, const uint32_t* hashes,
-                        uint64_t n, const uint8_t* rows, uint64_t row_stride, uint8_t bit, uint32_t V,
-                        const uint32_t* col, uint32_t id_cap, const uint8_t* truth, const uint8_t* active,
+static void route_views(Ring& r, const DevKeys& k, uint64_t n, const uint8_t* rows, uint64_t row_stride, uint8_t bit,
+                        uint32_t V, const uint32_t* col, uint32_t id_cap, const uint8_t* truth, const uint8_t* active,
                         int accumulate, uint64_t* wrong, uint64_t* lost, uint32_t* key_wrong, uint32_t* truth_owner,
                         uint32_t* owners, hipStream_t st) {
     const uint32_t idb = r.nt.size();
     RP_REQUIRE(id_cap >= idb, "route_views: id_cap is below the ring's id bound (rp_ring_id_bound)");
-    RP_REQUIRE(n == 0 || ((keys != nullptr) != (hashes != nullptr)),
+    RP_REQUIRE(n == 0 || ((k.keys != nullptr) != (k.hashes != nullptr)),
                "route_views: exactly one of the key buffer and the hash buffer");
-    RP_REQUIRE(n == 0 || hashes || stride || off, "route_views: null key offsets");
+    RP_REQUIRE(n == 0 || k.hashes || k.stride || k.off, "route_views: null key offsets");
     RP_REQUIRE(V == 0 || rows, "route_views: null view rows");
     RP_REQUIRE(bit != 0, "route_views: bit is zero");
     RP_REQUIRE(V == 0 || col || row_stride >= id_cap, "route_views: without a column map row_stride covers id_cap");
@@ -4839,18 +4772,17 @@ static void route_views(Ring& r, const uint8_t* keys, const uint64_t* off, uint3
     vblock = std::max<uint64_t>(64, vblock & ~63ull);
     const uint32_t VBW = (uint32_t)(vblock / 64), nvb = (PW + VBW - 1) / VBW;
     const size_t lds = (size_t)std::min(VBW, PW) * 128u * sizeof(uint32_t);
-    const bool fixed36 = !hashes && stride == 36 && ((reinterpret_cast<uintptr_t>(keys) & 3) == 0);
+    const bool fixed36 = k.fixed36();
     const RingView rv = r.view();
     const uint64_t gcap = (uint64_t)cu_count(r.device) * 4;  // 512 threads at <= 64 VGPRs: four workgroups a CU
     for (uint64_t k0 = 0; k0 < n; k0 += kRouteChunk) {
         const uint32_t cnt = (uint32_t)std::min<uint64_t>(kRouteChunk, n - k0);
         const unsigned g = (unsigned)std::max<uint64_t>(
             1, std::min<uint64_t>(gcap, ((uint64_t)cnt + kRouteThreads - 1) / kRouteThreads));
-#define RP_ROUTE(FIXED, OWN)                                                                                        \
-    hipLaunchKernelGGL((k_route<FIXED, OWN>), dim3(g, nvb), dim3(kRouteThreads), lds, st,                          \
-                       hashes ? nullptr : (stride ? keys + k0 * stride : keys),                                    \
-                       (!hashes && !stride) ? off + k0 : nullptr, stride, hashes ? hashes + k0 : nullptr, cnt, rv, \
-                       ws.plane.p, any, act, tany, ws.tr.p, PW, V, VBW,                                            \
+        const DevKeys c = k.from(k0);
+#define RP_ROUTE(FIXED, OWN)                                                                                       \
+    hipLaunchKernelGGL((k_route<FIXED, OWN>), dim3(g, nvb), dim3(kRouteThreads), lds, st, c.keys, c.off, c.stride, \
+                       c.hashes, cnt, rv, ws.plane.p, any, act, tany, ws.tr.p, PW, V, VBW,                         \
                        reinterpret_cast<unsigned long long*>(wrong), reinterpret_cast<unsigned long long*>(lost),  \
                        key_wrong ? key_wrong + k0 : nullptr, truth_owner ? truth_owner + k0 : nullptr,             \
                        owners ? owners + k0 * V : nullptr)
@@ -5125,28 +5057,23 @@ static void require_keys(const char* op, const KeySrc& k, uint64_t n, bool rest 
 // The host forms' staging, on r.st through the handle's buffers: hashes -> io_a; else the key
 // bytes -> io_keys (with 16 bytes of tail for the kernels' wide loads) and, without a stride, the
 // offsets -> io_off. n == 0 stages nothing. The pointers are what the rp:: passes take.
-struct DevKeys {
-    const uint8_t* dk;
-    const uint64_t* doff;
-    const uint32_t* dh;
-};
-static DevKeys stage_keys(rp::Ring& r, const KeySrc& k, uint64_t n) {
-    DevKeys d{nullptr, nullptr, nullptr};
+static rp::DevKeys stage_keys(rp::Ring& r, const KeySrc& k, uint64_t n) {
+    rp::DevKeys d{nullptr, nullptr, k.stride, nullptr};
     if (n == 0) return d;
     if (k.hashed) {
         r.io_a.reserve(n);
         RP_HIP(hipMemcpyAsync(r.io_a.p, k.hashes, n * 4, hipMemcpyHostToDevice, r.st));
-        d.dh = r.io_a.p;
+        d.hashes = r.io_a.p;
         return d;
     }
     const uint64_t bytes = k.stride ? n * k.stride : k.off[n];
     r.io_keys.reserve(bytes + 16);
     RP_HIP(hipMemcpyAsync(r.io_keys.p, k.keys, bytes, hipMemcpyHostToDevice, r.st));
-    d.dk = r.io_keys.p;
+    d.keys = r.io_keys.p;
     if (!k.stride) {
         r.io_off.reserve(n + 1);
         RP_HIP(hipMemcpyAsync(r.io_off.p, k.off, (n + 1) * 8, hipMemcpyHostToDevice, r.st));
-        d.doff = r.io_off.p;
+        d.off = r.io_off.p;
     }
     return d;
 }
@@ -5633,10 +5560,10 @@ static void host_lookup(rp::Ring& r, const KeySrc& k, uint64_t n, int np, uint32
     rp::QuietScope quiet;  // the launch path: no resident service (this ring's or another's) meanwhile
     svc_stop(r);
     if (!k.hashed && host_lookup_small(r, k.keys, k.off, k.stride, n, np, W, owners, counts)) return;
-    const DevKeys d = stage_keys(r, k, n);
+    const rp::DevKeys d = stage_keys(r, k, n);
     r.io_b.reserve(n * W);
     if (counts) r.io_cnt.reserve(n);
-    rp::launch_lookupn(r, d.dk, d.doff, k.stride, d.dh, n, np, W, r.io_b.p, counts ? r.io_cnt.p : nullptr, r.st);
+    rp::launch_lookupn(r, d.keys, d.off, d.stride, d.hashes, n, np, W, r.io_b.p, counts ? r.io_cnt.p : nullptr, r.st);
     RP_HIP(hipMemcpyAsync(owners, r.io_b.p, n * W * 4, hipMemcpyDeviceToHost, r.st));
     if (counts) RP_HIP(hipMemcpyAsync(counts, r.io_cnt.p, n, hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
@@ -5712,7 +5639,7 @@ static void host_group(rp::Ring& r, const KeySrc& k, uint64_t n, uint32_t self_i
                        uint32_t* perm, uint32_t* ndest) {
     RP_REQUIRE(dests && goff && perm && ndest, "group_keys: null output buffer");
     svc_stop(r);
-    const DevKeys d = stage_keys(r, k, n);
+    const rp::DevKeys d = stage_keys(r, k, n);
     // io_b = [perm n | group_off n+1 | dests n | ndest 1]
     const uint64_t nn = n ? n : 1;
     r.io_b.reserve(3 * nn + 2);
@@ -5720,7 +5647,7 @@ static void host_group(rp::Ring& r, const KeySrc& k, uint64_t n, uint32_t self_i
     uint32_t* dgoff = dperm + nn;
     uint32_t* ddest = dgoff + nn + 1;
     uint32_t* dnd = ddest + nn;
-    rp::group_keys(r, d.dk, d.doff, k.stride, d.dh, n, self_id, ddest, dgoff, dperm, dnd, r.st);
+    rp::group_keys(r, d.keys, d.off, d.stride, d.hashes, n, self_id, ddest, dgoff, dperm, dnd, r.st);
     uint32_t nd = 0;
     RP_HIP(hipMemcpyAsync(&nd, dnd, 4, hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
@@ -5826,7 +5753,7 @@ int rp_ring_moved_keys_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t
         const rp::Snap& s = S(before);
         require_keys("moved_keys_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
-        rp::moved_keys(r, s, d_keys, d_off, stride, nullptr, n, nrep, cap, d_idx, d_before, d_after, d_count,
+        rp::moved_keys(r, s, {d_keys, d_off, stride, nullptr}, n, nrep, cap, d_idx, d_before, d_after, d_count,
                        rp::as_stream(stream));
     });
 }
@@ -5839,7 +5766,7 @@ static void host_moved(rp::Ring& r, const rp::Snap& s, const KeySrc& k, uint64_t
     RP_REQUIRE(n < (1ull << 32), "moved_keys: at most 2^32-1 keys per call");
     RP_REQUIRE(cap == 0 || n == 0 || idx, "moved_keys: null index buffer");
     svc_stop(r);
-    const DevKeys d = stage_keys(r, k, n);
+    const rp::DevKeys d = stage_keys(r, k, n);
     // io_b = [count 1 | idx c | before rows c*W | after rows c*W], c = min(cap, n)
     const uint64_t c = std::min<uint64_t>(cap, n), W = rp::replicas(nrep, r.server_count).W;
     r.io_b.reserve(1 + c * (1 + 2 * W));
@@ -5847,7 +5774,7 @@ static void host_moved(rp::Ring& r, const rp::Snap& s, const KeySrc& k, uint64_t
     uint32_t* didx = dcount + 1;
     uint32_t* dbr = didx + c;
     uint32_t* dar = dbr + c * W;
-    rp::moved_keys(r, s, d.dk, d.doff, k.stride, d.dh, n, nrep, (uint32_t)c, c ? didx : nullptr, brows ? dbr : nullptr,
+    rp::moved_keys(r, s, d, n, nrep, (uint32_t)c, c ? didx : nullptr, brows ? dbr : nullptr,
                    arows ? dar : nullptr, dcount, r.st);
     uint32_t total = 0;
     RP_HIP(hipMemcpyAsync(&total, dcount, 4, hipMemcpyDeviceToHost, r.st));
@@ -5897,7 +5824,7 @@ int rp_ring_handoff_dev(rp_ring* h, const rp_ring_snap* before, const uint8_t* d
         const rp::Snap& s = S(before);
         require_keys("handoff_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
-        rp::handoff(r, s, d_keys, d_off, stride, nullptr, n, nrep, only_src, cap, d_dests, d_group_off, d_key_idx,
+        rp::handoff(r, s, {d_keys, d_off, stride, nullptr}, n, nrep, only_src, cap, d_dests, d_group_off, d_key_idx,
                     d_src, d_slot, d_ndest, d_count, rp::as_stream(stream), false);
     });
 }
@@ -5914,7 +5841,7 @@ static void host_handoff(rp::Ring& r, const rp::Snap& s, const KeySrc& k, uint64
     RP_REQUIRE(only_src == rp::NIL || only_src < r.nt.size(), "handoff: only_src is not a server id of this ring");
     RP_REQUIRE(cap == 0 || n == 0 || (dests && goff && key_idx), "handoff: null output buffer");
     svc_stop(r);
-    const DevKeys d = stage_keys(r, k, n);
+    const rp::DevKeys d = stage_keys(r, k, n);
     // io = [count 1 | ndest 1 | group_off nd+1 | dests nd | key_idx c | src c | slot c bytes],
     // c = min(cap, n * W), nd = min(c, id bound)
     const uint64_t c = std::min<uint64_t>(cap, n * W), nd = std::min<uint64_t>(c, r.nt.size());
@@ -5926,7 +5853,7 @@ static void host_handoff(rp::Ring& r, const rp::Snap& s, const KeySrc& k, uint64
     uint32_t* dki = dde + nd;
     uint32_t* dsr = dki + c;
     uint8_t* dsl = reinterpret_cast<uint8_t*>(dsr + c);
-    rp::handoff(r, s, d.dk, d.doff, k.stride, d.dh, n, nrep, only_src, (uint32_t)c, dde, dgo, dki, dsr, dsl,
+    rp::handoff(r, s, d, n, nrep, only_src, (uint32_t)c, dde, dgo, dki, dsr, dsl,
                 ws.io.p + 1, ws.io.p, r.st, true);
     uint32_t head[2] = {0, 0};
     RP_HIP(hipMemcpyAsync(head, ws.io.p, sizeof head, hipMemcpyDeviceToHost, r.st));
@@ -5980,7 +5907,7 @@ int rp_ring_route_views_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d
     return guard([&] {
         rp::Ring& r = R(h);
         svc_stop(r);
-        rp::route_views(r, d_keys, d_off, stride, d_hashes, n, d_rows, row_stride, bit, n_views, d_col, id_cap,
+        rp::route_views(r, {d_keys, d_off, stride, d_hashes}, n, d_rows, row_stride, bit, n_views, d_col, id_cap,
                         d_truth, d_active, accumulate, d_wrong, d_lost, d_key_wrong, d_truth_owner, d_owners,
                         rp::as_stream(stream));
     });
@@ -6000,14 +5927,14 @@ int rp_ring_route_views(rp_ring* h, const char* keys, const uint64_t* off, uint3
         RP_REQUIRE(n == 0 || hashes || stride || off, "route_views: null key offsets");
         RP_REQUIRE(V == 0 || rows, "route_views: null view rows");
         svc_stop(r);
-        const DevKeys d = stage_keys(r, hashes ? key_hashes(hashes) : key_bytes(keys, off, stride), n);
+        const rp::DevKeys d = stage_keys(r, hashes ? key_hashes(hashes) : key_bytes(keys, off, stride), n);
         // the uint32 outputs: [key_wrong n | truth_owner n | owners n * V]
         const DevViews dv = stage_views(r, rows, row_stride, V, col, truth, active, accumulate, wrong, lost,
                                         2 * n + n * V);
         uint32_t* dkw = key_wrong ? dv.out32 : nullptr;
         uint32_t* dto = truth_owner ? dv.out32 + n : nullptr;
         uint32_t* dow = owners ? dv.out32 + 2 * n : nullptr;
-        rp::route_views(r, d.dk, d.doff, stride, d.dh, n, dv.rows, row_stride, bit, n_views, dv.col, id_cap, dv.truth,
+        rp::route_views(r, d, n, dv.rows, row_stride, bit, n_views, dv.col, id_cap, dv.truth,
                         dv.active, accumulate, dv.wrong, dv.lost, dkw, dto, dow, r.st);
         unstage_views(r, dv, V, wrong, lost);
         if (n) {
@@ -6066,7 +5993,7 @@ int rp_ring_owner_load_dev(rp_ring* h, const uint8_t* d_keys, const uint64_t* d_
         rp::Ring& r = R(h);
         require_keys("owner_load_dev", key_bytes(d_keys, d_off, stride), n);
         svc_stop(r);
-        rp::owner_load(r, r.load_ws, d_keys, d_off, stride, nullptr, n, nrep, id_cap, accumulate,
+        rp::owner_load(r, r.load_ws, {d_keys, d_off, stride, nullptr}, n, nrep, id_cap, accumulate,
                        reinterpret_cast<unsigned long long*>(d_load), rp::as_stream(stream));
     });
 }
@@ -6078,10 +6005,10 @@ static void host_owner_load(rp::Ring& r, const KeySrc& k, uint64_t n, int32_t nr
     svc_stop(r);
     const uint64_t bins = (uint64_t)id_cap * rp::replicas(nrep, r.server_count).W;
     if (bins == 0) return;
-    const DevKeys d = stage_keys(r, k, n);
+    const rp::DevKeys d = stage_keys(r, k, n);
     r.load_ws.use_on(r.st);
     r.load_ws.out.reserve(bins);
-    rp::owner_load(r, r.load_ws, d.dk, d.doff, k.stride, d.dh, n, nrep, id_cap, 0, r.load_ws.out.p, r.st);
+    rp::owner_load(r, r.load_ws, d, n, nrep, id_cap, 0, r.load_ws.out.p, r.st);
     RP_HIP(hipMemcpyAsync(load, r.load_ws.out.p, bins * sizeof(uint64_t), hipMemcpyDeviceToHost, r.st));
     RP_HIP(hipStreamSynchronize(r.st));
 }
@@ -6119,8 +6046,8 @@ int rp_ring_snap_owner_load_dev(rp_ring_snap* s, const uint8_t* d_keys, const ui
         rp::owner_load_walk(d.load_ws, n, nrep, d.id_bound, id_cap, d.M != 0, accumulate,
                             reinterpret_cast<unsigned long long*>(d_load), d.device, st,
                             [&](uint64_t k0, uint64_t cnt, uint32_t* rows) {
-                                rp::launch_lookupn_view(d.view(), stride ? d_keys + k0 * stride : d_keys,
-                                                        stride ? nullptr : d_off + k0, stride, nullptr, cnt, rep.np, rep.W,
+                                const rp::DevKeys c = rp::DevKeys{d_keys, d_off, stride, nullptr}.from(k0);
+                                rp::launch_lookupn_view(d.view(), c.keys, c.off, c.stride, c.hashes, cnt, rep.np, rep.W,
                                                         rows, nullptr, st, rp::lookup_knobs().ablate);
                             });
     });

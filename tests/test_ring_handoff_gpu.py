@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import handoff_model as hm
+import ring_key_forms as kf
 from test_ring_moved_gpu import SENT, _keys, changed_pair, dev_keys, names_for, oracle_rows, to_gpu_ids
 
 torch = pytest.importorskip("torch")
@@ -122,6 +123,20 @@ def handoff_dev(ring, snap, keys_ptr, n, nrep, cap, alloc, only_src=NIL, opt=Tru
     return int(u32(cnt)[0]), int(u32(ndest)[0]), u32(dests), u32(goff), u32(kidx), u32(src), slot.cpu().numpy()
 
 
+def handoff_hashes(gpu, ring, snap, hashes, nrep, cap, alloc, only_src=NIL):
+    """rp_ring_handoff_hashes over sentinel-filled host outputs, shaped as handoff_dev's result."""
+    nd = ring.id_bound() + 8
+    full = lambda k: np.full(k, SENT, dtype=np.uint32)  # noqa: E731
+    dests, goff, kidx, src = full(nd), full(nd + 1), full(max(alloc, 1)), full(max(alloc, 1))
+    slot = np.full(max(alloc, 1), 0x5A, dtype=np.uint8)
+    ndest, cnt = ctypes.c_uint32(SENT), ctypes.c_uint32(SENT)
+    h = np.ascontiguousarray(hashes, dtype=np.uint32)
+    gpu.check(gpu.lib().rp_ring_handoff_hashes(ring._h, snap._h, h.ctypes.data, len(h), nrep, only_src, cap,
+                                               dests.ctypes.data, goff.ctypes.data, kidx.ctypes.data, src.ctypes.data,
+                                               slot.ctypes.data, ctypes.byref(ndest), ctypes.byref(cnt)))
+    return cnt.value, ndest.value, dests, goff, kidx, src, slot
+
+
 def assert_dev(res, want, cap, id_bound):
     """The device result equals the model's plan and nothing at or past the stated capacities
     (dests: min(cap, id bound), group_off: one more, key_idx / src / slot: cap) is touched."""
@@ -227,36 +242,10 @@ def test_key_forms_on_a_side_stream(gpu, orc, nrep):
     n = 2055
     side = torch.cuda.Stream()
     kw = {"stream": side.cuda_stream}
-    fixed = np.array(_keys(n))
-    short = np.ascontiguousarray(fixed[:, :20])
-    var = [bytes(fixed[i, :1 + (i * 5) % 36]) for i in range(n)]  # mixed lengths, 1..36 bytes
-
-    def rows_of(o, hashes):
-        out = np.full((n, max(nrep, 1)), NIL, dtype=np.uint32)
-        for i, h in enumerate(hashes):
-            r = o.lookupn_hash(h, nrep)
-            out[i, :len(r)] = r
-        return out
-
-    var_hashes = [orc.hash32(k) for k in var]
-    for form in ("aligned", "lead4", "offsets", "stride20"):
+    for form in kf.FORMS:
         ring, snap, ob, oa, nnames, change = queued_change(gpu, orc)
-        if form in ("aligned", "lead4"):
-            lead = 0 if form == "aligned" else 4
-            buf = dev_keys(gpu, n, lead=lead)
-            ptr, extra = buf.data_ptr() + lead, {}
-            wb, _ = ob.lookupn_keys(fixed, nrep)
-            wa, _ = oa.lookupn_keys(fixed, nrep)
-        elif form == "stride20":
-            buf = torch.from_numpy(short.reshape(-1)).cuda()
-            ptr, extra = buf.data_ptr(), {"stride": 20}
-            wb, _ = ob.lookupn_keys(short, nrep)
-            wa, _ = oa.lookupn_keys(short, nrep)
-        else:
-            buf = torch.from_numpy(np.frombuffer(b"".join(var) + b"\0" * 16, dtype=np.uint8).copy()).cuda()
-            off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(k) for k in var])]).astype(np.int64)).cuda()
-            ptr, extra = buf.data_ptr(), {"stride": 0, "off_ptr": off.data_ptr()}
-            wb, wa = rows_of(ob, var_hashes), rows_of(oa, var_hashes)
+        ptr, extra, keep = kf.device_side(form, n)
+        wb, wa = kf.oracle_rows(ob, form, n, nrep), kf.oracle_rows(oa, form, n, nrep)
         torch.cuda.synchronize()
         ring.addRemoveServers(*change)  # queued just before the call on the other stream
         wb, wa = to_gpu_ids(ring, oa, wb, nnames), to_gpu_ids(ring, oa, wa, nnames)
@@ -264,7 +253,10 @@ def test_key_forms_on_a_side_stream(gpu, orc, nrep):
         want = hm.plan(wb, wa, mask)
         assert want[5] > 0, form
         cap = want[5] + 9
-        res = handoff_dev(ring, snap, ptr, n, nrep, cap, cap + 8, **extra, **kw)
+        if form == "hashes":  # (the host entry point: the ring's own stream)
+            res = handoff_hashes(gpu, ring, snap, keep, nrep, cap, cap + 8)
+        else:
+            res = handoff_dev(ring, snap, ptr, n, nrep, cap, cap + 8, **extra, **kw)
         assert_dev(res, want, cap, ring.id_bound())
         snap.close()
         ring.close()

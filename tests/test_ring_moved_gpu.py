@@ -13,6 +13,8 @@ import functools
 import numpy as np
 import pytest
 
+import ring_key_forms as kf
+
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
@@ -253,6 +255,34 @@ def test_generic_unaligned_base(gpu, orc, n):
     cnt, idx, br, ar = moved_dev(ring, snap, buf4.data_ptr() + 4, n, 3, n, n)
     assert cnt == len(want) and np.array_equal(idx[:cnt], want)
     assert np.array_equal(br[:cnt], wb[want]) and np.array_equal(ar[:cnt], wa[want])
+
+
+@pytest.mark.parametrize("form", kf.FORMS)
+@pytest.mark.parametrize("nrep", [1, 3, 8])
+def test_key_forms(gpu, orc, nrep, form):
+    """Every key form through every kernel shape (rows of 1, up to 4, up to 8 owners). 2,055 keys:
+    two full 1,024-key tiles + 7 and four full 512-key tiles + 7, so a launch has full tiles and a
+    partial last one."""
+    n = 2055
+    ring, snap, ob, oa, nnames = changed_pair(gpu, orc, 64, 1, 1)
+    wb = to_gpu_ids(ring, oa, kf.oracle_rows(ob, form, n, nrep), nnames)
+    wa = to_gpu_ids(ring, oa, kf.oracle_rows(oa, form, n, nrep), nnames)
+    ptr, extra, keep = kf.device_side(form, n)
+    if form == "hashes":  # (only the host entry point takes them)
+        w = max(nrep, 1)
+        idx = np.full(n, SENT, dtype=np.uint32)
+        br, ar = np.full((n, w), SENT, dtype=np.uint32), np.full((n, w), SENT, dtype=np.uint32)
+        c = ctypes.c_uint32(SENT)
+        gpu.check(gpu.lib().rp_ring_moved_hashes(ring._h, snap._h, keep.ctypes.data, n, nrep, n, idx.ctypes.data,
+                                                 br.ctypes.data, ar.ctypes.data, ctypes.byref(c)))
+        cnt = c.value
+    else:
+        cnt, idx, br, ar = moved_dev(ring, snap, ptr, n, nrep, n, n, **extra)
+    assert 0 < cnt < n
+    assert (idx[cnt:] == SENT).all() and (br[cnt:] == SENT).all() and (ar[cnt:] == SENT).all()
+    assert assert_moved((idx[:cnt], br[:cnt], ar[:cnt]), wb, wa, n) == cnt
+    snap.close()
+    ring.close()
 
 
 def hash_func_case(gpu, orc, hf, servers, nkeys, nrep):
