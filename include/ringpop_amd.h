@@ -751,13 +751,24 @@ int rp_sim_join_exchange_local(rp_sim *const *shards, uint32_t nshards);
  *                  never completes, and the step (or rp_sim_join_export) that reaches the event
  *                  fails with RP_EINVAL. A sharded handle takes joins through rp_sim_join_export /
  *                  rp_sim_join_import.
- * Convergence then reads: every node that is up and has not left holds the same checksum, each
+ *   RP_SIM_SIDE    the node moves to side `reserved` (0..255, else RP_EINVAL) of the network.
+ *                  side[N] is one byte a node, 0 for everyone at creation, global on every shard.
+ *                  A sender v reaches u when u is up and side[v] == side[u]; a node across the cut
+ *                  is to v exactly what a down node is: it gets no ping, gives no answer and
+ *                  cannot help a ping-req (a helper v reaches is on v's side and cannot reach v's
+ *                  target either, so pingStatus stays false). It differs from a down node only in
+ *                  running its own rounds on its side. A partition is a batch of these in one
+ *                  round. Kill, revive, leave and join keep the node's side; a join is answered
+ *                  by live nodes on the joiner's side (none: RP_EINVAL, as above).
+ *   RP_SIM_HEAL    every node's side becomes 0 (`node` is ignored; it must still be < n).
+ *                  Message loss, one-way links and delays are not modelled.
+ * `reserved` is read only by RP_SIM_SIDE. Convergence is global, with or without a cut, and reads: every node that is up and has not left holds the same checksum, each
  * member that left is `leave` and each other member that is down `faulty` in those views.
  * dead[] = down from the start (never started gossip; gossip/index.js:97 never shuffled). */
 typedef struct rp_sim_event {
     uint32_t round, kind, node, reserved;
 } rp_sim_event;
-enum { RP_SIM_KILL = 0, RP_SIM_REVIVE = 1, RP_SIM_LEAVE = 2, RP_SIM_JOIN = 3 };
+enum { RP_SIM_KILL = 0, RP_SIM_REVIVE = 1, RP_SIM_LEAVE = 2, RP_SIM_JOIN = 3, RP_SIM_SIDE = 4, RP_SIM_HEAL = 5 };
 int rp_sim_create_scenario(uint32_t n, const char *names, const uint32_t *off, const int64_t *inc0,
                            const uint8_t *dead, uint32_t seed, uint32_t suspicion_rounds, int64_t now0, int device,
                            const uint32_t *bounds, uint32_t nshards, uint32_t shard, const rp_sim_event *events,
@@ -819,6 +830,23 @@ int rp_sim_routing_share(rp_sim *s, rp_ring *ring, const uint8_t *truth,
  * RP_CENSUS_ROWS (read per call) sets the rows a workgroup covers. */
 int rp_sim_census(rp_sim *s, const uint8_t *observe, const int64_t *max_ref, uint32_t *n_obs, uint32_t *status,
                   uint32_t *in_ring, int64_t *max_inc, uint32_t *at_max, uint32_t *behind);
+/* Every node's side of the network now (the RP_SIM_SIDE / RP_SIM_HEAL events applied so far):
+ * side[N], global, the same on every shard. */
+int rp_sim_sides(rp_sim *s, uint8_t *side);
+/* Convergence per side, on the handle's stream after the rounds queued so far. Observers: the
+ * handle's nodes that rp_sim_converged compares (up and not left). Four arrays of 256 entries by
+ * side id, each nullable:
+ *   nodes[s]           observers on side s
+ *   ck_min[s], ck_max[s]  the range of their checksums; 0xFFFFFFFF and 0 where nodes[s] == 0
+ *   cross_pingable[s]  #{(observer v on s, member a) : a is down or on another side, and v holds a
+ *                      as alive or suspect} (Member.isPingable)
+ * A side has settled when ck_min == ck_max and cross_pingable == 0. Over the shards of a sharded
+ * simulator nodes and cross_pingable add up and the min / max combine; a sharded handle answers
+ * only at a round boundary (before stage 0), else RP_EINVAL. Host buffers, synchronous; the scratch
+ * belongs to the handle. Two launches: the count and range (one wave reduction per side present in
+ * a wave), then a sweep of the observers' status rows, one wave a row, made only when
+ * cross_pingable is asked for. */
+int rp_sim_side_summary(rp_sim *s, uint32_t *nodes, uint32_t *ck_min, uint32_t *ck_max, uint64_t *cross_pingable);
 
 /* Stream-ordered copy between any host / device buffers (hipMemcpyDefault); NULL stream =
  * synchronous. Used by hosts that move sharded-simulator messages. */

@@ -156,6 +156,8 @@ SIGNATURES = {
     "rp_sim_routing_hashes": (_INT, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "rp_sim_routing_share": (_INT, [_P, _P, _P, _P, _P, _P, _U32]),
     "rp_sim_census": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rp_sim_sides": (_INT, [_P, _P]),
+    "rp_sim_side_summary": (_INT, [_P, _P, _P, _P, _P]),
     "rp_members_defer_checksum": (_INT, [_P, _INT]),
     "rp_members_checksum_shard": (_INT, [_P, _U32, _U32, _U32]),
     "rp_members_checksum_history": (_INT, [_P, _P, _P, _U32, _P]),
@@ -1323,14 +1325,17 @@ class PartMembership(Membership):
         return Membership.dump(self)
 
 
-SIM_EVENT = {"kill": 0, "revive": 1, "leave": 2, "join": 3}
+SIM_EVENT = {"kill": 0, "revive": 1, "leave": 2, "join": 3, "side": 4, "heal": 5}
+SIM_SIDES = 256
 
 
 def _events(events):
-    """(round, kind, node) triples -> rp_sim_event[] (uint32 x 4 each); kind a SIM_EVENT name or code."""
+    """(round, kind, node) or (round, kind, node, arg) -> rp_sim_event[] (uint32 x 4 each); kind a
+    SIM_EVENT name or code; arg (0 when left out) is the side of a "side" event."""
     ev = np.zeros((max(len(events), 1), 4), dtype=np.uint32)
-    for i, (r, k, v) in enumerate(events):
-        ev[i, :3] = (int(r), SIM_EVENT.get(k, k), int(v))
+    for i, e in enumerate(events):
+        r, k, v = e[:3]
+        ev[i] = (int(r), SIM_EVENT.get(k, k), int(v), int(e[3]) if len(e) > 3 else 0)
     return ev, len(events)
 
 
@@ -1355,7 +1360,8 @@ _CENSUS_FIELDS = ("observers", "status", "in_ring", "max_inc", "at_max", "behind
 class GossipSim:
     """N full ringpop nodes advanced in the deterministic gossip round model on the device
     (DESIGN.md §SWIM round model; oracle/orc_sim.c restates it on the CPU). events: scenario
-    (round, kind, node) triples, kind in SIM_EVENT (include/ringpop_amd.h "Scenarios")."""
+    (round, kind, node) triples, kind in SIM_EVENT (include/ringpop_amd.h "Scenarios"); a network
+    partition is a batch of (round, "side", node, side) in one round, (round, "heal", 0) ends it."""
 
     def __init__(self, names, inc0, dead, seed=11, suspicion_rounds=25, now0=None, device=0, events=()):
         self.N = len(names)
@@ -1483,6 +1489,41 @@ class GossipSim:
         check(lib().rp_sim_census(self._h, _ptr(ob), _ptr(mr), ctypes.byref(n_obs), *outs))
         res["observers"] = n_obs.value
         return res
+
+    def sides(self):
+        """Every node's side of the network now (uint8[N], global): 0 until a "side" event."""
+        out = np.empty(self.N, dtype=np.uint8)
+        check(lib().rp_sim_sides(self._h, out.ctypes.data))
+        return out
+
+    def side_summary(self):
+        """Convergence per side of the network (rp_sim_side_summary), arrays of SIM_SIDES entries by
+        side id over this handle's nodes that are up and have not left: {"nodes": uint32, "ck_min",
+        "ck_max": uint32 (0xFFFFFFFF and 0 for an empty side), "cross_pingable": uint64, the (node,
+        member) pairs where the member is down or across the cut and the node still holds it alive
+        or suspect, "settled": bool, ck_min == ck_max and cross_pingable == 0}."""
+        res = {"nodes": np.zeros(SIM_SIDES, dtype=np.uint32), "ck_min": np.zeros(SIM_SIDES, dtype=np.uint32),
+               "ck_max": np.zeros(SIM_SIDES, dtype=np.uint32), "cross_pingable": np.zeros(SIM_SIDES, dtype=np.uint64)}
+        check(lib().rp_sim_side_summary(self._h, *(res[k].ctypes.data for k in _SIDE_FIELDS)))
+        return _side_settled(res)
+
+
+_SIDE_FIELDS = ("nodes", "ck_min", "ck_max", "cross_pingable")
+
+
+def _side_settled(res):
+    res["settled"] = (res["ck_min"] == res["ck_max"]) & (res["cross_pingable"] == 0)
+    return res
+
+
+def side_summary_reduce(parts):
+    """One side summary from the shards' (GossipSim.side_summary results): nodes and cross_pingable
+    add up, the checksum ranges combine."""
+    parts = list(parts)
+    return _side_settled({"nodes": np.sum([p["nodes"] for p in parts], axis=0, dtype=np.uint32),
+                          "ck_min": np.min([p["ck_min"] for p in parts], axis=0),
+                          "ck_max": np.max([p["ck_max"] for p in parts], axis=0),
+                          "cross_pingable": np.sum([p["cross_pingable"] for p in parts], axis=0, dtype=np.uint64)})
 
 
 def census_reduce(parts):
@@ -1618,6 +1659,8 @@ class SimShard:
     routing = GossipSim.routing
     routing_share = GossipSim.routingShare
     census = GossipSim.census
+    sides = GossipSim.sides
+    side_summary = GossipSim.side_summary
 
 
 def conv_reduce(parts):
@@ -1714,7 +1757,7 @@ class ShardedGossipSim:
         handle's truth), gathered over the shards."""
         up = ~np.asarray(self._dead, dtype=bool)
         rnd = self.round
-        for r, k, v in sorted(self._events, key=lambda e: int(e[0])):
+        for r, k, v in sorted((e[:3] for e in self._events), key=lambda e: int(e[0])):
             if int(r) >= rnd:
                 break
             k = SIM_EVENT.get(k, k)
@@ -1751,6 +1794,13 @@ class ShardedGossipSim:
         default, together the unsharded one (every handle holds the global dead[])."""
         ref = np.max([s.census(observe, want=("max_inc",))["max_inc"] for s in self.shards], axis=0)
         return census_reduce([s.census(observe, max_ref=ref) for s in self.shards])
+
+    def sides(self):
+        return self.shards[0].sides()
+
+    def side_summary(self):
+        """GossipSim.side_summary over the shards (side_summary_reduce)."""
+        return side_summary_reduce([s.side_summary() for s in self.shards])
 
 
 class _DeviceBytes:
@@ -2014,6 +2064,18 @@ class DistGossipSim:
         for k in ("status", "in_ring", "at_max"):
             res[k] = self._allreduce(part[k], ops.SUM).astype(np.uint32)
         return res
+
+    def sides(self):
+        return self.shard.sides()
+
+    def side_summary(self):
+        """ShardedGossipSim.side_summary across the ranks: every rank's part gathered, then
+        side_summary_reduce."""
+        part = self.shard.side_summary()
+        cols = self._allgather(np.stack([part[k].astype(np.int64) for k in _SIDE_FIELDS]))
+        dt = (np.uint32, np.uint32, np.uint32, np.uint64)
+        return side_summary_reduce([{k: c[i].astype(t) for i, (k, t) in enumerate(zip(_SIDE_FIELDS, dt))}
+                                    for c in cols])
 
 
 # ------------------------------------------------------------------ gossip wire bodies

@@ -156,6 +156,7 @@ struct SimDev {
     uint32_t *n_shuf, *ring_count, *max_piggy, *checksum;
     uint8_t* dirty;
     const uint8_t* dead;  // [N] (global): down this round (never started, crashed, suspended)
+    const uint8_t* side;  // [N] (global): the node's side of the network, 0 until an event cuts it
     uint8_t* stopped;     // [NL] own status became leave: gossip.stop() + suspicion.stopAll()
     // names in address order; base checksum string (global)
     const uint32_t* sorted;
@@ -216,6 +217,14 @@ __device__ __forceinline__ uint32_t shard_of(const SimDev& S, uint32_t v) {
     uint32_t s = 0;
     while (s + 1 < S.G && v >= S.bounds[s + 1]) s++;
     return s;
+}
+
+// What a sender v sees of another node u: u answers when it is up and on v's side of the network.
+// A node across a cut is to v what a down node is (no ping arrives, no answer, no ping-req help);
+// it differs only in running its own rounds on its side. Sides are equivalence classes, so a
+// helper v can reach cannot reach v's unreachable target either (pingStatus stays false).
+__device__ __forceinline__ bool reach(const SimDev& S, uint32_t v, uint32_t u) {
+    return !S.dead[u] && S.side[v] == S.side[u];
 }
 
 __device__ __forceinline__ uint32_t philox_u32(uint32_t seed, uint32_t tag, uint32_t c0, uint32_t c1, uint32_t c2) {
@@ -2502,7 +2511,7 @@ __global__ void k_early_list(SimDev S, uint32_t* __restrict__ list, uint32_t* __
         bool on = lv < S.NL && S.dirty[lv] && !S.dead[S.v0 + lv];
         if (on) {
             const int32_t t = S.target[lv];
-            on = !(t >= 0 && S.dead[t]);
+            on = !(t >= 0 && !reach(S, S.v0 + lv, (uint32_t)t));
             // a view whose earliest suspicion timer is due fires it in phase E and changes again
             // (timers are appended with due = round + susp, so the head timer is the earliest)
             const uint32_t th = S.t_head[lv];
@@ -2614,13 +2623,13 @@ __global__ __launch_bounds__(kT) void k_phase_c(SimDev S) {
     }
 }
 
-// The live local senders whose target is dead (the ping-req senders of D1), in any order (their
-// work is independent); every node's helper count is reset.
+// The live local senders whose target is dead or across a cut (the ping-req senders of D1), in any
+// order (their work is independent); every node's helper count is reset.
 __global__ void k_d1_list(SimDev S, uint32_t* __restrict__ list, uint32_t* __restrict__ n) {
     for (uint32_t lv = blockIdx.x * blockDim.x + threadIdx.x; lv < S.NL; lv += gridDim.x * blockDim.x) {
         S.nhelp[lv] = 0;
         const int32_t t = S.target[lv];
-        if (!S.dead[S.v0 + lv] && t >= 0 && S.dead[t]) list[atomicAdd(n, 1u)] = lv;
+        if (!S.dead[S.v0 + lv] && t >= 0 && !reach(S, S.v0 + lv, (uint32_t)t)) list[atomicAdd(n, 1u)] = lv;
     }
 }
 
@@ -3104,18 +3113,18 @@ __global__ void k_join_finish(SimDev S, uint32_t v, uint32_t* __restrict__ scrat
 // ---- outboxes: messages grouped by destination shard
 
 // Candidate c of a message kind: its destination shard (G = none) and the sort value c.
-//   K_PING  c = local sender        -> shard of its live target
-//   K_LEG   c = local sender * 3 + k -> shard of helper k (live helpers only)
+//   K_PING  c = local sender        -> shard of its target, when the sender reaches it
+//   K_LEG   c = local sender * 3 + k -> shard of helper k (the helpers the sender reaches only)
 //   K_RESP / K_LRESP c = inbound message (receive order) -> shard of its sender
 __global__ void k_out_keys(SimDev S, int kind, uint32_t C, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < C; c += gridDim.x * blockDim.x) {
         uint32_t k = S.G;
         if (kind == K_PING) {
             const int32_t t = S.target[c];
-            if (!S.dead[S.v0 + c] && t >= 0 && !S.dead[t]) k = shard_of(S, (uint32_t)t);
+            if (!S.dead[S.v0 + c] && t >= 0 && reach(S, S.v0 + c, (uint32_t)t)) k = shard_of(S, (uint32_t)t);
         } else if (kind == K_LEG) {
             const uint32_t lv = c / 3, j = c % 3;
-            if (j < S.nhelp[lv] && !S.dead[S.helpers[c]]) k = shard_of(S, S.helpers[c]);
+            if (j < S.nhelp[lv] && reach(S, S.v0 + lv, S.helpers[c])) k = shard_of(S, S.helpers[c]);
         } else {
             k = shard_of(S, S.in_msg[c].from);
         }
@@ -3294,6 +3303,93 @@ __global__ void k_conv_local(SimDev S, const uint8_t* __restrict__ skip, const u
         const uint32_t lv = (uint32_t)(i / nk), w = want[i % nk], a = w & 0xFFFFFFu;
         if (skip[S.v0 + lv]) continue;
         if ((S.st[(uint64_t)lv * S.N + a] & ST_MASK) != (w >> 24)) out[3] = 1;
+    }
+}
+
+// ---- rp_sim_side_summary: the convergence question asked per side of the network. The observers
+// are conv_local's (skip clear). tab = {nodes [256], min checksum [256], max checksum [256]} by side
+// id; cross [256] counts the pairs (observer v, member a) where a is down or on another side than v
+// and v's row still holds a as alive or suspect (Member.isPingable).
+// Two launches, no workgroup waits for another.
+constexpr uint32_t kSides = 256;
+
+// Count and checksum range: one wave reduction per side present in the wave (a loop over the
+// distinct sides of its lanes, wave-uniform), then one atomic of each kind into the side's entries.
+__global__ __launch_bounds__(256) void k_side_ck(SimDev S, const uint8_t* __restrict__ skip, uint32_t* __restrict__ tab) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < S.NL; i0 += stride) {
+        const uint32_t lv = i0 + threadIdx.x;
+        const bool obs = lv < S.NL && !skip[S.v0 + lv];
+        const uint32_t sd = obs ? S.side[S.v0 + lv] : 0u;
+        const uint32_t c = obs ? S.checksum[lv] : 0u;
+        uint64_t left = __ballot(obs);
+        while (left) {  // wave-uniform
+            const uint32_t s0 = (uint32_t)__shfl((int)sd, __ffsll((long long)left) - 1, 64);
+            const bool mine = obs && sd == s0;
+            uint32_t cnt = mine ? 1u : 0u, lo = mine ? c : 0xFFFFFFFFu, hi = mine ? c : 0u;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                cnt += __shfl_xor(cnt, o, 64);
+                const uint32_t l2 = __shfl_xor(lo, o, 64), h2 = __shfl_xor(hi, o, 64);
+                lo = l2 < lo ? l2 : lo;
+                hi = h2 > hi ? h2 : hi;
+            }
+            if (lane == 0) {
+                atomicAdd(&tab[s0], cnt);
+                atomicMin(&tab[kSides + s0], lo);
+                atomicMax(&tab[2 * kSides + s0], hi);
+            }
+            left &= ~__ballot(mine);
+        }
+    }
+}
+
+// a status byte's share of cross_pingable: member a held alive or suspect while down or across
+__device__ __forceinline__ uint32_t side_cross_byte(const SimDev& S, uint32_t b, uint32_t a, uint32_t sv) {
+    const uint32_t st = b & ST_MASK;
+    return ((st == ST_ALIVE || st == ST_SUSPECT) && (S.dead[a] || S.side[a] != sv)) ? 1u : 0u;
+}
+
+// The row sweep: one wave per observer's status row (1 B a member). The bytes up to the row's
+// first 16-byte boundary and those after its last go one to a lane; between them a lane takes 16
+// members a load, with their down and side bytes (those 16 start at any byte of their arrays).
+// One 64-bit atomic per row, into the observer's side.
+__global__ __launch_bounds__(256) void k_side_cross(SimDev S, const uint8_t* __restrict__ skip,
+                                                    unsigned long long* __restrict__ cross) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    for (uint32_t lv = wave; lv < S.NL; lv += nwaves) {  // wave-uniform
+        const uint32_t v = S.v0 + lv;
+        if (skip[v]) continue;
+        const uint32_t sv = S.side[v];
+        const uint8_t* row = S.st + (uint64_t)lv * S.N;
+        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(row) & 15u);
+        const uint32_t head = min(S.N, (16u - mis) & 15u);
+        const uint32_t chunks = (S.N - head) >> 4, tail0 = head + (chunks << 4);
+        uint32_t n = 0;
+        if (lane < head) n += side_cross_byte(S, row[lane], lane, sv);
+        for (uint32_t a = tail0 + lane; a < S.N; a += 64u) n += side_cross_byte(S, row[a], a, sv);
+        for (uint32_t q = lane; q < chunks; q += 64u) {
+            const uint32_t a0 = head + (q << 4);
+            const uint4 w = *reinterpret_cast<const uint4*>(row + a0);
+            uint4 dd, ss;
+            __builtin_memcpy(&dd, S.dead + a0, 16);
+            __builtin_memcpy(&ss, S.side + a0, 16);
+            const uint32_t wb[4] = {w.x, w.y, w.z, w.w}, db[4] = {dd.x, dd.y, dd.z, dd.w}, sb[4] = {ss.x, ss.y, ss.z, ss.w};
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t st = (wb[k] >> (8 * j)) & ST_MASK;
+                    const bool away = ((db[k] >> (8 * j)) & 0xFFu) != 0 || ((sb[k] >> (8 * j)) & 0xFFu) != sv;
+                    n += ((st == ST_ALIVE || st == ST_SUSPECT) && away) ? 1u : 0u;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+        if (lane == 0 && n) atomicAdd(&cross[sv], (unsigned long long)n);
     }
 }
 
@@ -3625,7 +3721,7 @@ struct Sim {
     unsigned grid = 0;
     NameTable nt;
     SimDev d{};
-    DevBuf<uint8_t> st_, dirty, dead, strbuf, sbase, stopped, cskip;
+    DevBuf<uint8_t> st_, dirty, dead, side, strbuf, sbase, stopped, cskip;
     DevBuf<int64_t> inc, it_idx, inc_snap, inc0;
     DevBuf<int32_t> target;
     DevBuf<uint32_t> slot;
@@ -3647,7 +3743,7 @@ struct Sim {
     DevBuf<unsigned long long> stats, cursor;
     MsgBuf out, in;
     Scratch ws;
-    std::vector<uint8_t> h_dead, h_left;
+    std::vector<uint8_t> h_dead, h_left, h_side;
     std::vector<uint32_t> h_bounds;
     std::vector<rp_sim_event> events;  // the scenario, by round
     size_t next_event = 0;
@@ -3666,6 +3762,7 @@ struct Sim {
     // rp_sim_census: the observer mask, the rank-ordered accumulators and the outputs' device
     // copies (CensusDev), sized at the first call; the host's mask
     DevBuf<uint8_t> cs_u8;
+    DevBuf<uint64_t> ss_tab;  // rp_sim_side_summary: cross [256], then nodes, min, max [256 each]
     DevBuf<uint32_t> cs_u32;
     DevBuf<int64_t> cs_i64;
     std::vector<uint8_t> cs_obs;
@@ -4005,8 +4102,9 @@ struct Sim {
             throw Error(RP_ESTATE, "sim: a view's kept twin fingerprint differs from its rows (RP_SIM_TWIN_VERIFY)");
     }
 
-    // The scenario's events of this round, before phase A: a node goes down or comes back (every
-    // shard keeps the global down flags), or leaves (on the shard that owns it).
+    // The scenario's events of this round, before phase A: a node goes down or comes back, or moves
+    // to a side of the network (every shard keeps the global down flags and sides), or leaves (on
+    // the shard that owns it).
     DevBuf<uint32_t> join_scratch;
 
     // leaves collected so far run before anything that reads the views (a join)
@@ -4036,9 +4134,9 @@ struct Sim {
     void join_begin(uint32_t v) {
         std::vector<uint32_t> cand;
         for (uint32_t u = 0; u < N; u++)
-            if (u != v && !h_dead[u]) cand.push_back(u);
+            if (u != v && !h_dead[u] && h_side[u] == h_side[v]) cand.push_back(u);  // reach(v, u)
         const uint32_t nj = (uint32_t)std::min<size_t>(3, cand.size());
-        RP_REQUIRE(nj > 0, "sim: a join needs at least one live node to answer it");
+        RP_REQUIRE(nj > 0, "sim: a join needs at least one live node on the joiner's side to answer it");
         for (uint32_t q = 0; q < nj; q++) {  // partial Fisher-Yates, JOIN stream
             const uint32_t r = philox4x32_10(U4{(uint32_t)round, q, v, 0u}, d.seed, TAG_JOIN).x;
             const uint32_t j = q + (uint32_t)(((uint64_t)r * (cand.size() - q)) >> 32);
@@ -4099,7 +4197,7 @@ struct Sim {
     // applied in place when this handle holds every node (stop_at_join false), else it is
     // begun (responders answer) and left for the join exchange. Returns true at such a join.
     bool apply_events_until_join(bool stop_at_join) {
-        bool down_changed = false;
+        bool down_changed = false, side_changed = false;
         std::vector<uint32_t> leaves;
         bool stopped = false;
         while (next_event < events.size() && events[next_event].round <= (uint64_t)round) {
@@ -4111,7 +4209,8 @@ struct Sim {
             if (e.kind == RP_SIM_JOIN) {
                 flush_leaves(leaves);
                 if (down_changed) RP_HIP(hipMemcpyAsync(dead.p, h_dead.data(), N, hipMemcpyHostToDevice, st));
-                down_changed = false;
+                if (side_changed) RP_HIP(hipMemcpyAsync(side.p, h_side.data(), N, hipMemcpyHostToDevice, st));
+                down_changed = side_changed = false;
                 if (stop_at_join) {
                     next_event++;
                     join_begin(e.node);
@@ -4129,6 +4228,16 @@ struct Sim {
                 const uint8_t dv = e.kind == RP_SIM_KILL ? 1 : 0;
                 down_changed |= h_dead[e.node] != dv;
                 h_dead[e.node] = dv;
+            } else if (e.kind == RP_SIM_SIDE) {
+                side_changed |= h_side[e.node] != (uint8_t)e.reserved;
+                h_side[e.node] = (uint8_t)e.reserved;
+                continue;  // (convergence does not read the sides)
+            } else if (e.kind == RP_SIM_HEAL) {
+                for (uint32_t u = 0; u < N; u++) {
+                    side_changed |= h_side[u] != 0;
+                    h_side[u] = 0;
+                }
+                continue;
             } else if (!h_dead[e.node]) {
                 // k_leave refuses a redundant leave by the node's own status: a node that left and
                 // then refuted a suspicion is alive again and may leave once more (h_left only
@@ -4141,8 +4250,9 @@ struct Sim {
             conv_dirty = true;
         }
         if (down_changed) RP_HIP(hipMemcpyAsync(dead.p, h_dead.data(), N, hipMemcpyHostToDevice, st));
+        if (side_changed) RP_HIP(hipMemcpyAsync(side.p, h_side.data(), N, hipMemcpyHostToDevice, st));
         flush_leaves(leaves);
-        if (down_changed) RP_HIP(hipStreamSynchronize(st));  // host vectors reused
+        if (down_changed || side_changed) RP_HIP(hipStreamSynchronize(st));  // host vectors reused
         return stopped;
     }
     void apply_events() { apply_events_until_join(false); }
@@ -4174,8 +4284,8 @@ struct Sim {
     }
 
     // {live, min checksum, max checksum, some wanted member not at its wanted status}
-    void conv_local(uint32_t* out4) {
-        refresh_checksums();
+    // the nodes convergence leaves out (down or left) and the statuses it wants, on the device
+    void conv_prepare() {
         if (conv_dirty) {
             std::vector<uint32_t> w;
             std::vector<uint8_t> skip(N);
@@ -4192,6 +4302,10 @@ struct Sim {
             RP_HIP(hipStreamSynchronize(st));
             conv_dirty = false;
         }
+    }
+    void conv_local(uint32_t* out4) {
+        refresh_checksums();
+        conv_prepare();
         const uint32_t init[4] = {0u, 0xFFFFFFFFu, 0u, 0u};
         RP_HIP(hipMemcpyAsync(conv.p, init, sizeof init, hipMemcpyHostToDevice, st));
         if (NL) {
@@ -4235,7 +4349,9 @@ static void sim_create(uint32_t n, const char* names, const uint32_t* off, const
     RP_REQUIRE(out && n >= 2 && names && off && inc0 && dead, "sim_create: bad arguments");
     RP_REQUIRE(n_events == 0 || events, "sim_create: events missing");
     for (uint32_t i = 0; i < n_events; i++)
-        RP_REQUIRE(events[i].node < n && events[i].kind <= RP_SIM_JOIN, "sim_create: bad event");
+        RP_REQUIRE(events[i].node < n && events[i].kind <= RP_SIM_HEAL &&
+                       (events[i].kind != RP_SIM_SIDE || events[i].reserved <= 255),
+                   "sim_create: bad event");
     RP_REQUIRE(n < (1u << 23), "sim_create: at most 2^23 members");
     RP_REQUIRE(nshards >= 1 && nshards <= rp::kMaxShards && shard < nshards, "sim_create: bad shard");
     std::vector<uint32_t> bnd(nshards + 1);
@@ -4302,9 +4418,11 @@ static void sim_create(uint32_t n, const char* names, const uint32_t* off, const
         // row moves, refutations included), so a node's changes and timers are bounded by them.
         std::vector<uint8_t> touched(dead, dead + n);
         uint32_t nrevive = 0;
+        // A cut makes the nodes of each side suspect those of the others: everyone is touched.
         for (uint32_t i = 0; i < n_events; i++) {
             touched[events[i].node] = 1;
             nrevive += events[i].kind == RP_SIM_REVIVE;
+            if (events[i].kind == RP_SIM_SIDE) std::fill(touched.begin(), touched.end(), 1);
         }
         uint32_t ndead = 0;
         for (uint32_t i = 0; i < n; i++) ndead += touched[i];
@@ -4327,7 +4445,7 @@ static void sim_create(uint32_t n, const char* names, const uint32_t* off, const
         S.chg.reserve(L1 * cap); S.tim.reserve(L1 * cap);
         S.n_chg.reserve(L1); S.n_tim.reserve(L1); S.t_head.reserve(L1); S.vfp.reserve(L1); S.vdt.reserve(L1); S.p1buf.reserve(L1);
         S.it_idx.reserve(L1); S.n_shuf.reserve(L1); S.ring_count.reserve(L1); S.max_piggy.reserve(L1);
-        S.checksum.reserve(L1); S.dirty.reserve(L1); S.dead.reserve(n); S.target.reserve(L1); S.ck_snap.reserve(L1);
+        S.checksum.reserve(L1); S.dirty.reserve(L1); S.dead.reserve(n); S.side.reserve(n); S.target.reserve(L1); S.ck_snap.reserve(L1);
         S.inc_snap.reserve(L1); S.ping_n.reserve(L1); S.leg_n.reserve(L1);
         S.helpers.reserve(3 * L1); S.nhelp.reserve(L1); S.leg_nk.reserve(3 * L1);
         S.resp_idx.reserve(L1); S.lresp_idx.reserve(3 * L1);
@@ -4370,6 +4488,8 @@ static void sim_create(uint32_t n, const char* names, const uint32_t* off, const
         RP_HIP(hipMemcpyAsync(S.bounds.p, bnd.data(), 4ull * (nshards + 1), hipMemcpyHostToDevice, S.st));
         S.h_dead.assign(dead, dead + n);
         RP_HIP(hipMemcpyAsync(S.dead.p, S.h_dead.data(), n, hipMemcpyHostToDevice, S.st));
+        S.h_side.assign(n, 0);
+        RP_HIP(hipMemsetAsync(S.side.p, 0, n, S.st));
         RP_HIP(hipMemsetAsync(S.stats.p, 0, 8 * sizeof(unsigned long long), S.st));
         RP_HIP(hipMemsetAsync(S.err.p, 0, 4, S.st));
         RP_HIP(hipMemsetAsync(S.cursor.p, 0, 8, S.st));
@@ -4382,7 +4502,7 @@ static void sim_create(uint32_t n, const char* names, const uint32_t* off, const
         d.xcap = (uint32_t)std::max<uint64_t>(2, std::min<uint64_t>(rp::kXCap, env_u64("RP_SIM_D1_XCAP", rp::kXCap)));
         d.chg = S.chg.p; d.n_chg = S.n_chg.p; d.tim = S.tim.p; d.n_tim = S.n_tim.p; d.t_head = S.t_head.p; d.vfp = S.vfp.p; d.vdt = S.vdt.p; d.p1 = S.p1buf.p; d.p1_pre = 0;
         d.it_idx = S.it_idx.p; d.n_shuf = S.n_shuf.p; d.ring_count = S.ring_count.p; d.max_piggy = S.max_piggy.p;
-        d.checksum = S.checksum.p; d.dirty = S.dirty.p; d.dead = S.dead.p; d.stopped = S.stopped.p;
+        d.checksum = S.checksum.p; d.dirty = S.dirty.p; d.dead = S.dead.p; d.side = S.side.p; d.stopped = S.stopped.p;
         d.sorted = S.nt.sorted.p; d.rank = S.rank.p; d.names = S.nt.d_bytes.p; d.noff = S.nt.d_noff.p;
         d.sbase = S.sbase.p; d.boff = S.boff.p; d.inc0 = S.inc0.p;
         d.target = S.target.p; d.ck_snap = S.ck_snap.p; d.inc_snap = S.inc_snap.p;
@@ -4395,7 +4515,7 @@ static void sim_create(uint32_t n, const char* names, const uint32_t* off, const
         d.stats = S.stats.p; d.err = S.err.p; d.round = 0;
         {
             const void* ptrs[] = {d.st, d.inc, d.order, d.slot, d.dev, d.chg, d.n_chg, d.tim, d.n_tim, d.t_head, d.vfp, d.it_idx,
-                                  d.n_shuf, d.ring_count, d.max_piggy, d.checksum, d.dirty, d.dead, d.sorted,
+                                  d.n_shuf, d.ring_count, d.max_piggy, d.checksum, d.dirty, d.dead, d.side, d.sorted,
                                   d.rank, d.names, d.noff, d.sbase, d.boff, d.inc0, d.target, d.ck_snap,
                                   d.inc_snap, d.pool, d.cursor, d.ping_n, d.leg_n, d.helpers, d.nhelp, d.leg_nk,
                                   d.cand, d.strbuf, d.resp_idx, d.lresp_idx, d.stats, d.err, d.bounds, d.stopped};
@@ -4897,6 +5017,45 @@ int rp_sim_census(rp_sim* s, const uint8_t* observe, const int64_t* max_ref, uin
         if (max_inc) RP_HIP(hipMemcpyAsync(max_inc, C.o_max, 8ull * N, hipMemcpyDeviceToHost, S.st));
         if (at_max) RP_HIP(hipMemcpyAsync(at_max, C.o_at, 4ull * N, hipMemcpyDeviceToHost, S.st));
         if (behind) RP_HIP(hipMemcpyAsync(behind, C.o_behind, 4ull * NL, hipMemcpyDeviceToHost, S.st));
+        RP_HIP(hipStreamSynchronize(S.st));
+    });
+}
+
+int rp_sim_sides(rp_sim* s, uint8_t* side) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        RP_REQUIRE(side, "sim_sides: null output");
+        std::copy(S.h_side.begin(), S.h_side.end(), side);
+    });
+}
+
+int rp_sim_side_summary(rp_sim* s, uint32_t* nodes, uint32_t* ck_min, uint32_t* ck_max, uint64_t* cross_pingable) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        RP_REQUIRE(S.G == 1 || S.next_stage == 0,
+                   "sim_side_summary: a sharded handle answers at a round boundary (before stage 0)");
+        constexpr uint32_t K = rp::kSides;
+        S.refresh_checksums();
+        S.conv_prepare();
+        // cross [K] u64 | nodes [K], min [K], max [K] u32
+        S.ss_tab.reserve(K + 3 * K / 2);
+        unsigned long long* cross = reinterpret_cast<unsigned long long*>(S.ss_tab.p);
+        uint32_t* tab = reinterpret_cast<uint32_t*>(S.ss_tab.p + K);
+        RP_HIP(hipMemsetAsync(cross, 0, 8 * K + 4 * K, S.st));  // cross and nodes
+        RP_HIP(hipMemsetAsync(tab + K, 0xFF, 4 * K, S.st));
+        RP_HIP(hipMemsetAsync(tab + 2 * K, 0, 4 * K, S.st));
+        if (S.NL) {
+            hipLaunchKernelGGL(rp::k_side_ck, dim3(rp::grid_for(S.NL, 256, 1024)), dim3(256), 0, S.st, S.d, S.cskip.p,
+                               tab);
+            if (cross_pingable)
+                hipLaunchKernelGGL(rp::k_side_cross, dim3(rp::grid_for((uint64_t)S.NL * 64, 256, 16u * S.cu())),
+                                   dim3(256), 0, S.st, S.d, S.cskip.p, cross);
+        }
+        RP_HIP(hipGetLastError());
+        if (nodes) RP_HIP(hipMemcpyAsync(nodes, tab, 4 * K, hipMemcpyDeviceToHost, S.st));
+        if (ck_min) RP_HIP(hipMemcpyAsync(ck_min, tab + K, 4 * K, hipMemcpyDeviceToHost, S.st));
+        if (ck_max) RP_HIP(hipMemcpyAsync(ck_max, tab + 2 * K, 4 * K, hipMemcpyDeviceToHost, S.st));
+        if (cross_pingable) RP_HIP(hipMemcpyAsync(cross_pingable, cross, 8 * K, hipMemcpyDeviceToHost, S.st));
         RP_HIP(hipStreamSynchronize(S.st));
     });
 }

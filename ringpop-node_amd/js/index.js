@@ -465,17 +465,20 @@ function GossipSim(names, options) {
     requireDevice(this.device);
     var inc0 = options.inc0 instanceof Float64Array ? options.inc0 : Float64Array.from(options.inc0);
     var dead = options.dead ? Uint8Array.from(options.dead) : new Uint8Array(this.n);
-    // options.events: [[round, 'kill' | 'revive' | 'leave' | 'join', node], ...] (rp_sim_create_scenario)
-    var kinds = {kill: 0, revive: 1, leave: 2, join: 3};
+    // options.events: [[round, 'kill' | 'revive' | 'leave' | 'join', node], ...] and, for a network
+    // partition, [round, 'side', node, side] (a batch of them in one round) and [round, 'heal', 0]
+    // (rp_sim_create_scenario)
+    var kinds = {kill: 0, revive: 1, leave: 2, join: 3, side: 4, heal: 5};
     var evs = options.events || [];
-    var ev = new Uint32Array(3 * evs.length);
+    var ev = new Uint32Array(4 * evs.length);
     evs.forEach(function (e, i) {
-        ev[3 * i] = e[0];
-        ev[3 * i + 1] = typeof e[1] === 'string' ? kinds[e[1]] : e[1];
-        ev[3 * i + 2] = e[2];
+        ev[4 * i] = e[0];
+        ev[4 * i + 1] = typeof e[1] === 'string' ? kinds[e[1]] : e[1];
+        ev[4 * i + 2] = e[2];
+        ev[4 * i + 3] = e.length > 3 ? e[3] : 0;
     });
     this._h = native.simCreate(names, inc0, dead, options.seed || 0, options.suspicionRounds || 25,
-        options.now0 || 0, this.device, ev);
+        options.now0 || 0, this.device, ev, 4);
 }
 
 GossipSim.prototype.destroy = function destroy() { native.destroy(this._h); };
@@ -494,6 +497,17 @@ GossipSim.prototype.census = function census(observe) {
         mask = Uint8Array.from(observe, function (x) { return x ? 1 : 0; });
     }
     return native.simCensus(this._h, this.n, mask);
+};
+// Every node's side of the network now: Uint8Array(n), 0 until a 'side' event.
+GossipSim.prototype.sides = function sides() { return native.simSides(this._h, this.n); };
+// Convergence per side (rp_sim_side_summary), by side id 0..255 over the nodes that are up and have
+// not left: {nodes, ckMin, ckMax: Uint32Array(256), crossPingable: Float64Array(256), the (node,
+// member) pairs where the member is down or across the cut and still alive or suspect in the
+// node's view, settled: Array(256) of ckMin === ckMax && crossPingable === 0}.
+GossipSim.prototype.sideSummary = function sideSummary() {
+    var s = native.simSideSummary(this._h);
+    s.settled = Array.from(s.nodes, function (_, i) { return s.ckMin[i] === s.ckMax[i] && s.crossPingable[i] === 0; });
+    return s;
 };
 GossipSim.prototype.converged = function converged() { return native.simConverged(this._h); };
 GossipSim.prototype.stats = function stats() { return native.simStats(this._h); };

@@ -1422,7 +1422,16 @@ static napi_value js_members_damp_dump(napi_env env, napi_callback_info info) {
 // simCreate(names, inc0, dead, seed, suspicionRounds, now0, device[, events Uint32Array of
 // (round, kind, node) triples: RP_SIM_KILL / REVIVE / LEAVE / JOIN])
 static napi_value js_sim_create(napi_env env, napi_callback_info info) {
-    ARGS(8);
+    /* (names, inc0, dead, seed, suspicionRounds, now0, device, events[, words per event = 3]) */
+    size_t argc = 9;
+    napi_value argv[9];
+    NAPI_OK(napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+    if (argc < 8) {
+        napi_throw_type_error(env, NULL, "wrong number of arguments");
+        return NULL;
+    }
+    uint32_t ew = 3;
+    if (argc > 8) napi_get_value_uint32(env, argv[8], &ew);
     strpack_t s;
     if (strpack_from_array(env, argv[0], &s)) return NULL;
     size_t n1 = 0, n2 = 0;
@@ -1455,22 +1464,24 @@ static napi_value js_sim_create(napi_env env, napi_callback_info info) {
     if (argc > 7) napi_typeof(env, argv[7], &et);
     if (et == napi_object) {
         ev = (const uint32_t *)typed_data(env, argv[7], napi_uint32_array, &ne);
-        if (!ev || ne % 3) {
+        if (!ev || (ew != 3 && ew != 4) || ne % ew) {
             free(inc);
             strpack_free(&s);
-            napi_throw_type_error(env, NULL, "simCreate events must be a Uint32Array of (round, kind, node) triples");
+            napi_throw_type_error(env, NULL, "simCreate events must be a Uint32Array of (round, kind, node) triples, "
+                                             "or of (round, kind, node, arg) with 4 as the last argument");
             return NULL;
         }
     }
-    rp_sim_event *evs = (rp_sim_event *)calloc(ne / 3 + 1, sizeof(rp_sim_event));
-    for (size_t i = 0; i < ne / 3; i++) {
-        evs[i].round = ev[3 * i];
-        evs[i].kind = ev[3 * i + 1];
-        evs[i].node = ev[3 * i + 2];
+    rp_sim_event *evs = (rp_sim_event *)calloc(ne / ew + 1, sizeof(rp_sim_event));
+    for (size_t i = 0; i < ne / ew; i++) {
+        evs[i].round = ev[ew * i];
+        evs[i].kind = ev[ew * i + 1];
+        evs[i].node = ev[ew * i + 2];
+        evs[i].reserved = ew == 4 ? ev[ew * i + 3] : 0;
     }
     rp_sim *sim = NULL;
     int rc = rp_sim_create_scenario(s.n, s.bytes, s.off32, inc, dead, seed, susp, now64, dev, NULL, 1, 0, evs,
-                                    (uint32_t)(ne / 3), &sim);
+                                    (uint32_t)(ne / ew), &sim);
     free(evs);
     free(inc);
     strpack_free(&s);
@@ -1571,6 +1582,40 @@ static napi_value js_sim_census(napi_env env, napi_callback_info info) {
     napi_set_named_property(env, out, "maxInc", mx);
     napi_set_named_property(env, out, "atMax", at);
     napi_set_named_property(env, out, "behind", behind);
+    return out;
+}
+
+static napi_value js_sim_sides(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    handle_t *h = get_handle(env, argv[0], 3);
+    if (!h) return NULL;
+    uint32_t n = 0;
+    NAPI_OK(napi_get_value_uint32(env, argv[1], &n));
+    void *d = NULL;
+    napi_value out = new_typed(env, napi_uint8_array, n, 1, &d);
+    RP_OK(rp_sim_sides((rp_sim *)h->p, (uint8_t *)d));
+    return out;
+}
+
+/* rp_sim_side_summary: {nodes, ckMin, ckMax: Uint32Array(256), crossPingable: Float64Array(256)} */
+static napi_value js_sim_side_summary(napi_env env, napi_callback_info info) {
+    ARGS(1);
+    handle_t *h = get_handle(env, argv[0], 3);
+    if (!h) return NULL;
+    void *nd = NULL, *lo = NULL, *hi = NULL, *cd = NULL;
+    napi_value nodes = new_typed(env, napi_uint32_array, 256, 4, &nd);
+    napi_value ck_min = new_typed(env, napi_uint32_array, 256, 4, &lo);
+    napi_value ck_max = new_typed(env, napi_uint32_array, 256, 4, &hi);
+    napi_value cross = new_typed(env, napi_float64_array, 256, 8, &cd);
+    uint64_t c64[256];
+    RP_OK(rp_sim_side_summary((rp_sim *)h->p, (uint32_t *)nd, (uint32_t *)lo, (uint32_t *)hi, c64));
+    for (int i = 0; i < 256; i++) ((double *)cd)[i] = (double)c64[i];
+    napi_value out;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "nodes", nodes);
+    napi_set_named_property(env, out, "ckMin", ck_min);
+    napi_set_named_property(env, out, "ckMax", ck_max);
+    napi_set_named_property(env, out, "crossPingable", cross);
     return out;
 }
 
@@ -1859,6 +1904,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"ringMovedRanges", NULL, js_ring_moved_ranges, NULL, NULL, NULL, napi_default, NULL},
         {"ringSnapDump", NULL, js_ring_snap_dump, NULL, NULL, NULL, napi_default, NULL},
         {"simCensus", NULL, js_sim_census, NULL, NULL, NULL, napi_default, NULL},
+        {"simSides", NULL, js_sim_sides, NULL, NULL, NULL, napi_default, NULL},
+        {"simSideSummary", NULL, js_sim_side_summary, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later);
     return exports;
