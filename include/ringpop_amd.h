@@ -848,6 +848,61 @@ int rp_sim_sides(rp_sim *s, uint8_t *side);
  * cross_pingable is asked for. */
 int rp_sim_side_summary(rp_sim *s, uint32_t *nodes, uint32_t *ck_min, uint32_t *ck_max, uint64_t *cross_pingable);
 
+/* ---- Timeline: what happened, round by round, recorded on the device. While it is enabled every
+ * round ends (stage 4) by appending one record of cluster-wide aggregates to a ring of records on
+ * the handle's stream, with no wait of the host, so one read after rp_sim_step_async(R) returns R
+ * records. st_v(a), ring_v(a): observer v's row for member a. */
+typedef struct rp_sim_round_rec {   /* 128 bytes, 8-byte aligned, unused tail zero */
+    uint64_t round;          /* the round that just ended (0-based: the record of the first step of a
+                                fresh handle is round 0) */
+    uint32_t observers;      /* the handle's nodes rp_sim_converged compares: up and not left */
+    uint32_t ck_min, ck_max; /* range of their checksums; 0xFFFFFFFF and 0 when observers == 0 */
+    uint32_t reserved;
+    uint64_t pairs[4];       /* #(observer v, member a) by st_v(a): alive, suspect, faulty, leave;
+                                they sum to observers * N */
+    uint64_t in_ring;        /* #(observer v, member a) with ring_v(a) */
+    uint64_t unmet;          /* sum over the members convergence wants at a status (left -> leave, other
+                                down members -> faulty) of the observers NOT holding them there */
+    uint64_t false_faulty;   /* #(observer v, member a): a is itself up and has not left, and v holds it
+                                faulty or leave (a live server missing from v's ring) */
+    uint64_t stats[4];       /* pings, ping-reqs, full syncs, applied updates since creation (rp_sim_stats)
+                                as of the end of this round */
+    uint64_t tail[2];        /* zero */
+} rp_sim_round_rec;
+/* The observers and the wanted statuses are rp_sim_converged's, after the round's events, so
+ *   observers == 0 || (ck_min == ck_max && unmet == 0)
+ * is what rp_sim_converged (one shard; sharded: the reduction of rp_sim_converged_local) would have
+ * answered after that round. Over the shards of one simulator observers, pairs, in_ring, unmet,
+ * false_faulty and stats add up and ck_min / ck_max combine by min / max; that is why unmet is a
+ * count and not a flag.
+ * rp_sim_timeline_enable: cap > 0 records from the next round on and keeps the last cap rounds;
+ * it resets everything (records and first_seen become 0xFFFFFFFF), also when the timeline was
+ * already on. cap == 0 turns recording off and frees the buffers. The buffers (cap * 128 B of
+ * records, n * 3 * 4 B of first_seen, n * 5 * 4 B of per-rank counters, n * 2 B of flags) belong to
+ * the handle and are allocated here, never per round. A sharded handle takes the call only at a
+ * round boundary (before stage 0), else RP_EINVAL and nothing changes. RP_TIMELINE_ROWS (read
+ * here) sets the rows a workgroup of the bitmap pass covers. A handle that never enables the
+ * timeline launches, copies and waits for nothing new.
+ * rp_sim_timeline_read waits for the handle's stream as rp_sim_sync does (with its error check)
+ * and copies the kept records oldest first: *n = min(rounds recorded since enable, cap, cap_out),
+ * the newest ones when cap_out is the smaller; *first_round = out[0].round. The host knows both
+ * from its own round counter. first_seen[a*3 + (s-1)] (uint32 [n*3], nullable), s = suspect,
+ * faulty, leave: the first recorded round at whose end some observer held member a at status s,
+ * 0xFFFFFFFF if none did; the ring's wrapping does not touch it, and over shards it combines by
+ * min. Timeline off: *n = 0 and first_seen is left alone, no error. A sharded handle answers only
+ * at a round boundary (before stage 0), else RP_EINVAL.
+ * Cost of a recorded round: the refresh the next round's stage 0 would have run (that stage then
+ * finds nothing to hash unless events dirty views), the observer count of rp_sim_converged written
+ * into the record, one pass over the observers' deviation bitmaps gathering only the status byte
+ * of set bits (the census's tiling), and one thread per address rank folding the counters into
+ * the record.
+ * Not given, on purpose: a per-member round at which EVERY observer held a status (not a
+ * reduction of per-shard values; rp_sim_census answers it at any chosen round) and a per-side
+ * timeline (rp_sim_side_summary answers per side at any chosen round). */
+int rp_sim_timeline_enable(rp_sim *s, uint32_t cap);
+int rp_sim_timeline_read(rp_sim *s, rp_sim_round_rec *out, uint32_t cap_out, uint32_t *n, uint64_t *first_round,
+                         uint32_t *first_seen);
+
 /* Stream-ordered copy between any host / device buffers (hipMemcpyDefault); NULL stream =
  * synchronous. Used by hosts that move sharded-simulator messages. */
 int rp_copy(void *dst, const void *src, uint64_t bytes, void *stream);

@@ -158,6 +158,8 @@ SIGNATURES = {
     "rp_sim_census": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rp_sim_sides": (_INT, [_P, _P]),
     "rp_sim_side_summary": (_INT, [_P, _P, _P, _P, _P]),
+    "rp_sim_timeline_enable": (_INT, [_P, _U32]),
+    "rp_sim_timeline_read": (_INT, [_P, _P, _U32, _P, _P, _P]),
     "rp_members_defer_checksum": (_INT, [_P, _INT]),
     "rp_members_checksum_shard": (_INT, [_P, _U32, _U32, _U32]),
     "rp_members_checksum_history": (_INT, [_P, _P, _P, _U32, _P]),
@@ -1507,8 +1509,42 @@ class GossipSim:
         check(lib().rp_sim_side_summary(self._h, *(res[k].ctypes.data for k in _SIDE_FIELDS)))
         return _side_settled(res)
 
+    def timeline_enable(self, cap):
+        """Record one rp_sim_round_rec of cluster-wide aggregates at the end of every round from
+        the next one on, on the device, keeping the last `cap` rounds (rp_sim_timeline_enable).
+        Resets what was recorded; cap 0 turns recording off."""
+        check(lib().rp_sim_timeline_enable(self._h, int(cap)))
+        self._tl_cap = int(cap)
+
+    def timeline(self, last=None):
+        """The recorded rounds, oldest first (rp_sim_timeline_read; waits for the queued rounds):
+        a dict of arrays with one entry per record, "round" uint64, "observers", "ck_min", "ck_max"
+        uint32, "pairs" uint64 [n, 4] (alive, suspect, faulty, leave), "in_ring", "unmet",
+        "false_faulty" uint64, "stats" uint64 [n, 4], "converged" bool (what converged() would have
+        said after that round), and "first_seen" uint32 [N, 3]: per member the first recorded round
+        at whose end some observer held it suspect, faulty, leave (SIM_NEVER: none did). last: at
+        most that many of the newest records."""
+        cap = getattr(self, "_tl_cap", 0)
+        cap = cap if last is None else min(cap, int(last))
+        recs = np.zeros(cap, dtype=_TL_REC)
+        fs = np.full((self.N, 3), SIM_NEVER, dtype=np.uint32)
+        n, first = ctypes.c_uint32(), ctypes.c_uint64()
+        check(lib().rp_sim_timeline_read(self._h, recs.ctypes.data if cap else None, cap, ctypes.byref(n),
+                                         ctypes.byref(first), fs.ctypes.data))
+        res = {k: np.ascontiguousarray(recs[k][:n.value]) for k in _TL_FIELDS}
+        res["first_seen"] = fs
+        return _tl_converged(res)
+
 
 _SIDE_FIELDS = ("nodes", "ck_min", "ck_max", "cross_pingable")
+SIM_NEVER = 0xFFFFFFFF  # a timeline's first_seen entry: no recorded round
+# rp_sim_round_rec
+_TL_REC = np.dtype([("round", "<u8"), ("observers", "<u4"), ("ck_min", "<u4"), ("ck_max", "<u4"), ("reserved", "<u4"),
+                    ("pairs", "<u8", 4), ("in_ring", "<u8"), ("unmet", "<u8"), ("false_faulty", "<u8"),
+                    ("stats", "<u8", 4), ("tail", "<u8", 2)])
+assert _TL_REC.itemsize == 128
+_TL_SUM = ("observers", "pairs", "in_ring", "unmet", "false_faulty", "stats")
+_TL_FIELDS = ("round", "ck_min", "ck_max") + _TL_SUM
 
 
 def _side_settled(res):
@@ -1524,6 +1560,34 @@ def side_summary_reduce(parts):
                           "ck_min": np.min([p["ck_min"] for p in parts], axis=0),
                           "ck_max": np.max([p["ck_max"] for p in parts], axis=0),
                           "cross_pingable": np.sum([p["cross_pingable"] for p in parts], axis=0, dtype=np.uint64)})
+
+
+def _tl_converged(res):
+    res["converged"] = (res["observers"] == 0) | ((res["ck_min"] == res["ck_max"]) & (res["unmet"] == 0))
+    return res
+
+
+def timeline_reduce(parts):
+    """One timeline from the shards' (GossipSim.timeline results): the counts and stats add up, the
+    checksum ranges and first_seen combine by min / max / min. The parts must cover the same rounds
+    (ValueError otherwise)."""
+    parts = list(parts)
+    for p in parts[1:]:
+        if not np.array_equal(p["round"], parts[0]["round"]):
+            raise ValueError("timeline_reduce: the parts cover different rounds")
+    res = {"round": parts[0]["round"].copy()}
+    for k in _TL_SUM:
+        res[k] = np.sum([p[k] for p in parts], axis=0, dtype=parts[0][k].dtype)
+    res["ck_min"] = np.min([p["ck_min"] for p in parts], axis=0)
+    res["ck_max"] = np.max([p["ck_max"] for p in parts], axis=0)
+    res["first_seen"] = np.min([p["first_seen"] for p in parts], axis=0)
+    return _tl_converged(res)
+
+
+def rounds_to_convergence(tl):
+    """The round of a timeline's first converged record, or None."""
+    hit = np.flatnonzero(tl["converged"])
+    return int(tl["round"][hit[0]]) if len(hit) else None
 
 
 def census_reduce(parts):
@@ -1661,6 +1725,8 @@ class SimShard:
     census = GossipSim.census
     sides = GossipSim.sides
     side_summary = GossipSim.side_summary
+    timeline_enable = GossipSim.timeline_enable
+    timeline = GossipSim.timeline
 
 
 def conv_reduce(parts):
@@ -1801,6 +1867,14 @@ class ShardedGossipSim:
     def side_summary(self):
         """GossipSim.side_summary over the shards (side_summary_reduce)."""
         return side_summary_reduce([s.side_summary() for s in self.shards])
+
+    def timeline_enable(self, cap):
+        for s in self.shards:
+            s.timeline_enable(cap)
+
+    def timeline(self, last=None):
+        """GossipSim.timeline over the shards (timeline_reduce)."""
+        return timeline_reduce([s.timeline(last) for s in self.shards])
 
 
 class _DeviceBytes:
@@ -2076,6 +2150,28 @@ class DistGossipSim:
         dt = (np.uint32, np.uint32, np.uint32, np.uint64)
         return side_summary_reduce([{k: c[i].astype(t) for i, (k, t) in enumerate(zip(_SIDE_FIELDS, dt))}
                                     for c in cols])
+
+    def timeline_enable(self, cap):
+        self.shard.timeline_enable(cap)
+
+    def timeline(self, last=None):
+        """ShardedGossipSim.timeline across the ranks: the counts and stats all-reduced (SUM), the
+        checksum ranges and first_seen by MIN / MAX / MIN. Every rank must have recorded the same
+        rounds (ValueError otherwise)."""
+        ops = self.dist.ReduceOp
+        part = self.shard.timeline(last)
+        rounds = part["round"].astype(np.int64)
+        span = np.array([len(rounds), rounds[0] if len(rounds) else -1], dtype=np.int64)
+        lo, hi = self._allreduce(span, ops.MIN), self._allreduce(span, ops.MAX)  # (every rank makes both calls)
+        if not np.array_equal(lo, hi):
+            raise ValueError("timeline: the ranks cover different rounds")
+        res = {"round": part["round"]}
+        for k in _TL_SUM:
+            res[k] = self._allreduce(part[k], ops.SUM).astype(part[k].dtype)
+        res["ck_min"] = self._allreduce(part["ck_min"], ops.MIN).astype(np.uint32)
+        res["ck_max"] = self._allreduce(part["ck_max"], ops.MAX).astype(np.uint32)
+        res["first_seen"] = self._allreduce(part["first_seen"], ops.MIN).astype(np.uint32)
+        return _tl_converged(res)
 
 
 # ------------------------------------------------------------------ gossip wire bodies

@@ -3600,6 +3600,117 @@ __global__ __launch_bounds__(256) void k_census_finish(SimDev S, CensusDev C) {
     if (i < S.NL) C.o_behind[i] = C.obs[i] ? C.nlow[0] + C.acc[i] : 0u;
 }
 
+// ---- the timeline: one rp_sim_round_rec of aggregates per round ----
+// At the end of a round, after the refresh: k_tl_begin starts the round's slot, k_conv_ck counts
+// the observers and their checksum range into it, k_tl_count adds the observers' deviated rows to
+// per-rank counters (the census's tiling; only the status byte is gathered), and k_tl_finish, one
+// thread per rank, folds the counters into the slot and clears them for the next round.
+struct TlDev {
+    uint32_t* cnt;         // [N*4] by address rank: observers' deviated rows per status
+    uint32_t* ring;        // [N]   by address rank: observers' deviated rows in the ring
+    uint32_t* first_seen;  // [N*3] by member id: first recorded round with an observer at suspect, faulty, leave
+    const uint8_t* want;   // [N]   by member id: the status convergence wants of it (faulty, leave), 0: none
+    const uint8_t* elig;   // [N]   by node id: up and has not left (an observer where local)
+    rp_sim_round_rec* rec;  // the round's slot
+};
+
+static_assert(sizeof(rp_sim_round_rec) == 128 && offsetof(rp_sim_round_rec, ck_min) == 12 &&
+                  offsetof(rp_sim_round_rec, pairs) == 24 && offsetof(rp_sim_round_rec, false_faulty) == 72,
+              "the kernels write the record by these offsets");
+
+__global__ void k_tl_begin(rp_sim_round_rec* __restrict__ rec, uint64_t round) {
+    uint64_t* w = reinterpret_cast<uint64_t*>(rec);
+    const uint32_t i = threadIdx.x;
+    if (i < sizeof(rp_sim_round_rec) / 8)  // observers 0, ck_min 0xFFFFFFFF, ck_max 0, sums 0
+        w[i] = i == 0 ? round : i == 1 ? 0xFFFFFFFF00000000ull : 0ull;
+}
+
+__global__ __launch_bounds__(kCsThreads) void k_tl_count(SimDev S, CensusDev C, TlDev T) {
+    __shared__ uint32_t l_cnt[kCsRanks * 4];
+    __shared__ uint32_t l_ring[kCsRanks];
+    __shared__ uint32_t l_a[kCsRanks];  // sorted[] of the tile's ranks
+    const CensusTile Tl = census_tile(S, C);
+    for (uint32_t i = threadIdx.x; i < kCsRanks; i += kCsThreads) {
+        for (uint32_t s = 0; s < 4; s++) l_cnt[4 * i + s] = 0;
+        l_ring[i] = 0;
+        l_a[i] = Tl.k0 + i < S.N ? S.sorted[Tl.k0 + i] : 0u;
+    }
+    __syncthreads();
+    if (Tl.w < S.W) {
+        const uint32_t kl0 = (threadIdx.x % kCsWords) * 32u;
+        for (uint32_t rb = Tl.r0 + Tl.sub; rb < Tl.r1; rb += kCsRowsStep * kCsUnroll) {
+            uint32_t word[kCsUnroll];
+            for (uint32_t u = 0; u < kCsUnroll; u++) word[u] = census_word(S, C, Tl, rb + u * kCsRowsStep);
+            for (uint32_t u = 0; u < kCsUnroll; u++) {
+                uint32_t bits = word[u];
+                const uint64_t row = (uint64_t)(rb + u * kCsRowsStep) * S.N;
+                while (bits) {
+                    const uint32_t kl = kl0 + (uint32_t)__builtin_ctz(bits);
+                    bits &= bits - 1;
+                    const uint8_t st = S.st[row + l_a[kl]];
+                    atomicAdd(&l_cnt[4 * kl + (st & ST_MASK)], 1u);
+                    if (st & IN_RING) atomicAdd(&l_ring[kl], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < kCsRanks; i += kCsThreads) {
+        const uint32_t k = Tl.k0 + i;
+        if (k >= S.N) break;
+        for (uint32_t s = 0; s < 4; s++) {
+            const uint32_t c = l_cnt[4 * i + s];
+            if (c) atomicAdd(&T.cnt[4ull * k + s], c);
+        }
+        if (l_ring[i]) atomicAdd(&T.ring[k], l_ring[i]);
+    }
+}
+
+// One thread per rank. A rank's sums are at most NL < 2^23, so a wave's fit 32 bits.
+__global__ __launch_bounds__(256) void k_tl_finish(SimDev S, TlDev T) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t obs = T.rec->observers;
+    uint32_t v[7] = {0, 0, 0, 0, 0, 0, 0};  // pairs[0..3], in_ring, unmet, false_faulty
+    if (k < S.N) {
+        const uint32_t a = S.sorted[k];
+        const uint4 q = *reinterpret_cast<const uint4*>(T.cnt + 4ull * k);
+        const uint32_t c[4] = {q.x, q.y, q.z, q.w};
+        const uint32_t d = c[0] + c[1] + c[2] + c[3];  // every deviated row has exactly one status
+        const uint32_t clear = obs - d;                // (alive, in ring)
+        const uint32_t ring = T.ring[k];
+        if (d) {  // the next round starts from zero
+            *reinterpret_cast<uint4*>(T.cnt + 4ull * k) = uint4{0u, 0u, 0u, 0u};
+            T.ring[k] = 0;
+        }
+#pragma unroll
+        for (uint32_t s = 1; s < 4; s++) {
+            uint32_t* fs = T.first_seen + 3ull * a + (s - 1);
+            if (c[s] && *fs == NONE) *fs = (uint32_t)S.round;
+        }
+        v[0] = c[0] + clear;
+        v[1] = c[1];
+        v[2] = c[2];
+        v[3] = c[3];
+        v[4] = ring + clear;
+        const uint32_t w = T.want[a];
+        v[5] = w ? obs - (w == ST_LEAVE ? c[3] : c[2]) : 0u;
+        v[6] = T.elig[a] ? c[ST_FAULTY] + c[ST_LEAVE] : 0u;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int i = 0; i < 7; i++) v[i] += __shfl_xor(v[i], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        unsigned long long* sums = reinterpret_cast<unsigned long long*>(T.rec->pairs);  // pairs[4], in_ring, unmet, false_faulty
+#pragma unroll
+        for (int i = 0; i < 7; i++)
+            if (v[i]) atomicAdd(&sums[i], (unsigned long long)v[i]);
+    }
+    if (k == 0)
+        for (int i = 0; i < 4; i++) T.rec->stats[i] = S.stats[i];
+}
+
 __global__ void k_sim_init(SimDev S) {
     const uint64_t NN = (uint64_t)S.NL * S.N;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < NN; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -4075,6 +4186,7 @@ struct Sim {
                 hipLaunchKernelGGL(k_phase_d3, dim3(g), dim3(kT), 0, st, d);
                 hipLaunchKernelGGL(k_phase_e, dim3(g), dim3(kT), 0, st, d);
             }
+            if (tl_cap) timeline_record();
             round++;
             break;
         }
@@ -4299,6 +4411,13 @@ struct Sim {
             cskip.reserve(N);
             if (nwant) RP_HIP(hipMemcpyAsync(want.p, w.data(), 4ull * nwant, hipMemcpyHostToDevice, st));
             RP_HIP(hipMemcpyAsync(cskip.p, skip.data(), N, hipMemcpyHostToDevice, st));
+            std::vector<uint8_t> tl;
+            if (tl_cap) {  // the same two facts by member: wanted status | observer-eligible
+                tl.assign(2ull * N, 0);
+                for (uint32_t i = 0; i < nwant; i++) tl[w[i] & 0xFFFFFFu] = (uint8_t)(w[i] >> 24);
+                for (uint32_t a = 0; a < N; a++) tl[N + a] = skip[a] ? 0 : 1;
+                RP_HIP(hipMemcpyAsync(tl_u8.p, tl.data(), 2ull * N, hipMemcpyHostToDevice, st));
+            }
             RP_HIP(hipStreamSynchronize(st));
             conv_dirty = false;
         }
@@ -4316,6 +4435,92 @@ struct Sim {
         }
         RP_HIP(hipGetLastError());
         RP_HIP(hipMemcpyAsync(out4, conv.p, 16, hipMemcpyDeviceToHost, st));
+        RP_HIP(hipStreamSynchronize(st));
+    }
+
+    // The grid of a bitmap pass (k_census_count, k_census_behind, k_tl_count): column tiles x row
+    // slabs, by default a few workgroups a CU (kCsPerCu), the slab a multiple of the rows a step;
+    // `rows_env` sets the slab (tests: many and ragged slabs). Fills C.ntiles and C.rows.
+    unsigned census_grid(CensusDev& C, const char* rows_env) {
+        constexpr uint32_t kCsPerCu = 4;
+        C.ntiles = (d.W + kCsWords - 1) / kCsWords;
+        const uint64_t want_slabs = std::max<uint64_t>(1, ((uint64_t)kCsPerCu * cu() + C.ntiles - 1) / C.ntiles);
+        uint64_t rows = (NL + want_slabs - 1) / want_slabs;
+        rows = (rows + kCsRowsStep - 1) / kCsRowsStep * kCsRowsStep;
+        rows = env_pos(rows_env, rows);
+        const uint64_t max_slabs = 0x7FFFFFFFull / C.ntiles;
+        rows = std::max<uint64_t>(rows, (NL + max_slabs - 1) / max_slabs);
+        C.rows = (uint32_t)std::min<uint64_t>(rows, NL);
+        return (unsigned)(C.ntiles * (((uint64_t)NL + C.rows - 1) / C.rows));
+    }
+
+    // ---- the timeline (rp_sim_timeline_enable / _read): tl_cap > 0 while it records
+    uint32_t tl_cap = 0;
+    int64_t tl_round0 = 0;       // the first recorded round
+    DevBuf<uint64_t> tl_rec;     // [tl_cap] records of 128 B, round r in slot (r - tl_round0) % tl_cap
+    DevBuf<uint32_t> tl_u32;     // cnt [4N], ring [N] by rank | first_seen [3N] by member
+    DevBuf<uint8_t> tl_u8;       // want [N] | elig [N] (conv_prepare)
+    CensusDev tl_tile{};         // the bitmap pass's observers and tiling
+    unsigned tl_grid = 0;
+    static constexpr uint64_t kRecWords = sizeof(rp_sim_round_rec) / 8;
+
+    void timeline_enable(uint32_t cap) {
+        tl_cap = 0;
+        if (cap == 0) {
+            tl_rec.release();
+            tl_u32.release();
+            tl_u8.release();
+            return;
+        }
+        tl_rec.reserve(kRecWords * cap);
+        tl_u32.reserve(8ull * N);
+        tl_u8.reserve(2ull * N);
+        RP_HIP(hipMemsetAsync(tl_rec.p, 0xFF, sizeof(rp_sim_round_rec) * (uint64_t)cap, st));
+        RP_HIP(hipMemsetAsync(tl_u32.p, 0, 20ull * N, st));
+        RP_HIP(hipMemsetAsync(tl_u32.p + 5ull * N, 0xFF, 12ull * N, st));
+        tl_tile = CensusDev{};
+        tl_tile.obs = tl_u8.p + N + v0;  // a local node observes when it is eligible
+        tl_grid = NL ? census_grid(tl_tile, "RP_TIMELINE_ROWS") : 0;
+        tl_round0 = round;
+        tl_cap = cap;
+        conv_dirty = true;  // want | elig go up with the next conv_prepare
+    }
+
+    // the end of stage 4: the record of the round that just ran
+    void timeline_record() {
+        refresh_checksums();  // what the next stage 0 would hash
+        conv_prepare();
+        TlDev T{};
+        T.cnt = tl_u32.p;
+        T.ring = tl_u32.p + 4ull * N;
+        T.first_seen = tl_u32.p + 5ull * N;
+        T.want = tl_u8.p;
+        T.elig = tl_u8.p + N;
+        T.rec = reinterpret_cast<rp_sim_round_rec*>(tl_rec.p + kRecWords * (uint64_t)((round - tl_round0) % tl_cap));
+        hipLaunchKernelGGL(k_tl_begin, dim3(1), dim3(64), 0, st, T.rec, (uint64_t)round);
+        if (NL) {
+            hipLaunchKernelGGL(k_conv_ck, dim3(grid_for(NL, 256, 1024)), dim3(256), 0, st, d, cskip.p, &T.rec->observers);
+            hipLaunchKernelGGL(k_tl_count, dim3(tl_grid), dim3(kCsThreads), 0, st, d, tl_tile, T);
+        }
+        hipLaunchKernelGGL(k_tl_finish, dim3(grid_for(N, 256, 1u << 24)), dim3(256), 0, st, d, T);
+        RP_HIP(hipGetLastError());
+    }
+
+    void timeline_read(rp_sim_round_rec* out, uint32_t cap_out, uint32_t* n, uint64_t* first_round, uint32_t* first_seen) {
+        check_err();
+        const uint64_t kept = std::min<uint64_t>((uint64_t)(round - tl_round0), tl_cap);
+        const uint32_t cnt = tl_cap ? (uint32_t)std::min<uint64_t>(kept, cap_out) : 0;
+        if (n) *n = cnt;
+        if (first_round) *first_round = (uint64_t)round - cnt;
+        if (!tl_cap) return;
+        RP_REQUIRE(cnt == 0 || out, "sim_timeline_read: null output");
+        const uint64_t s0 = ((uint64_t)(round - tl_round0) - cnt) % tl_cap;  // the oldest returned record's slot
+        const uint64_t head = std::min<uint64_t>(cnt, tl_cap - s0);
+        if (head)
+            RP_HIP(hipMemcpyAsync(out, tl_rec.p + kRecWords * s0, sizeof(rp_sim_round_rec) * head, hipMemcpyDeviceToHost, st));
+        if (cnt > head)
+            RP_HIP(hipMemcpyAsync(out + head, tl_rec.p, sizeof(rp_sim_round_rec) * (cnt - head), hipMemcpyDeviceToHost, st));
+        if (first_seen) RP_HIP(hipMemcpyAsync(first_seen, tl_u32.p + 5ull * N, 12ull * N, hipMemcpyDeviceToHost, st));
         RP_HIP(hipStreamSynchronize(st));
     }
 };
@@ -4984,18 +5189,7 @@ int rp_sim_census(rp_sim* s, const uint8_t* observe, const int64_t* max_ref, uin
         int64_t* mref = C.ref + N;
         C.o_max = mref + N;
         C.n_obs = no;
-        // the grid: column tiles x row slabs, by default a few workgroups a CU (kCsPerCu), the slab
-        // a multiple of the rows a step; RP_CENSUS_ROWS sets the slab (tests: many and ragged slabs)
-        constexpr uint32_t kCsPerCu = 4;
-        C.ntiles = (S.d.W + rp::kCsWords - 1) / rp::kCsWords;
-        const uint64_t want_slabs = std::max<uint64_t>(1, ((uint64_t)kCsPerCu * S.cu() + C.ntiles - 1) / C.ntiles);
-        uint64_t rows = (NL + want_slabs - 1) / want_slabs;
-        rows = (rows + rp::kCsRowsStep - 1) / rp::kCsRowsStep * rp::kCsRowsStep;
-        rows = rp::env_pos("RP_CENSUS_ROWS", rows);
-        const uint64_t max_slabs = 0x7FFFFFFFull / C.ntiles;
-        rows = std::max<uint64_t>(rows, (NL + max_slabs - 1) / max_slabs);
-        C.rows = (uint32_t)std::min<uint64_t>(rows, NL);
-        const unsigned grid = (unsigned)(C.ntiles * (((uint64_t)NL + C.rows - 1) / C.rows));
+        const unsigned grid = S.census_grid(C, "RP_CENSUS_ROWS");
         const unsigned flat = rp::grid_for(std::max(N, NL), 256, 1u << 24);
         const bool second = at_max || behind;
         RP_HIP(hipMemcpyAsync(obs, S.cs_obs.data(), NL, hipMemcpyHostToDevice, S.st));
@@ -5071,6 +5265,25 @@ int rp_sim_converged(rp_sim* s, int* out) {
         uint32_t c[4];
         S.conv_local(c);
         *out = (c[0] == 0 || (c[1] == c[2] && c[3] == 0)) ? 1 : 0;
+    });
+}
+
+int rp_sim_timeline_enable(rp_sim* s, uint32_t cap) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        RP_REQUIRE(S.G == 1 || S.next_stage == 0,
+                   "sim_timeline_enable: a sharded handle takes the call at a round boundary (before stage 0)");
+        S.timeline_enable(cap);
+    });
+}
+
+int rp_sim_timeline_read(rp_sim* s, rp_sim_round_rec* out, uint32_t cap_out, uint32_t* n, uint64_t* first_round,
+                         uint32_t* first_seen) {
+    return guard([&] {
+        rp::Sim& S = SM(s);
+        RP_REQUIRE(S.G == 1 || S.next_stage == 0,
+                   "sim_timeline_read: a sharded handle answers at a round boundary (before stage 0)");
+        S.timeline_read(out, cap_out, n, first_round, first_seen);
     });
 }
 

@@ -509,6 +509,27 @@ GossipSim.prototype.sideSummary = function sideSummary() {
     s.settled = Array.from(s.nodes, function (_, i) { return s.ckMin[i] === s.ckMax[i] && s.crossPingable[i] === 0; });
     return s;
 };
+// Timeline (rp_sim_timeline_enable / rp_sim_timeline_read): from the next round on every round ends
+// by appending one record of cluster-wide aggregates on the device, the last `cap` are kept;
+// cap 0 turns it off. timeline() -> {firstRound, rounds: [{round, observers, ckMin, ckMax, pairs:
+// [alive, suspect, faulty, leave] (observer, member) pairs, inRing, unmet, falseFaulty, stats: [pings,
+// pingReqs, fullSyncs, applied], converged}], firstSeen: Uint32Array(3n) with [a * 3 + s - 1] the
+// first recorded round some observer held member a suspect / faulty / leave (0xFFFFFFFF: none)}.
+GossipSim.prototype.timelineEnable = function timelineEnable(cap) {
+    native.simTimelineEnable(this._h, cap);
+    this._tlCap = cap;
+};
+GossipSim.prototype.timeline = function timeline() {
+    var t = native.simTimelineRead(this._h, this.n, this._tlCap || 0);
+    var rounds = [];
+    for (var i = 0; i < t.count; i++) {
+        var r = t.recs.subarray(15 * i, 15 * i + 15);
+        rounds.push({round: r[0], observers: r[1], ckMin: r[2], ckMax: r[3], pairs: Array.from(r.subarray(4, 8)),
+            inRing: r[8], unmet: r[9], falseFaulty: r[10], stats: Array.from(r.subarray(11, 15)),
+            converged: r[1] === 0 || (r[2] === r[3] && r[9] === 0)});
+    }
+    return {firstRound: t.firstRound, rounds: rounds, firstSeen: t.firstSeen};
+};
 GossipSim.prototype.converged = function converged() { return native.simConverged(this._h); };
 GossipSim.prototype.stats = function stats() { return native.simStats(this._h); };
 

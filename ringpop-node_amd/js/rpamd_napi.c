@@ -1619,6 +1619,64 @@ static napi_value js_sim_side_summary(napi_env env, napi_callback_info info) {
     return out;
 }
 
+static napi_value js_sim_timeline_enable(napi_env env, napi_callback_info info) {
+    ARGS(2);
+    handle_t *h = get_handle(env, argv[0], 3);
+    if (!h) return NULL;
+    uint32_t cap = 0;
+    NAPI_OK(napi_get_value_uint32(env, argv[1], &cap));
+    RP_OK(rp_sim_timeline_enable((rp_sim *)h->p, cap));
+    return NULL;
+}
+
+/* simTimelineRead(handle, n, cap) -> {count, firstRound, recs: Float64Array(15 * count), per record
+ * {round, observers, ckMin, ckMax, pairs[4], inRing, unmet, falseFaulty, stats[4]} (every field is at
+ * most n^2 or a traffic count: exact in a double), firstSeen: Uint32Array(3n)} */
+static napi_value js_sim_timeline_read(napi_env env, napi_callback_info info) {
+    ARGS(3);
+    handle_t *h = get_handle(env, argv[0], 3);
+    if (!h) return NULL;
+    uint32_t n = 0, cap = 0;
+    NAPI_OK(napi_get_value_uint32(env, argv[1], &n));
+    NAPI_OK(napi_get_value_uint32(env, argv[2], &cap));
+    rp_sim_round_rec *recs = (rp_sim_round_rec *)malloc(sizeof(rp_sim_round_rec) * (cap ? cap : 1));
+    void *fd = NULL;
+    napi_value fs = new_typed(env, napi_uint32_array, 3 * (size_t)n, 4, &fd);
+    memset(fd, 0xFF, 12 * (size_t)n);
+    uint32_t cnt = 0;
+    uint64_t first = 0;
+    int rc = rp_sim_timeline_read((rp_sim *)h->p, recs, cap, &cnt, &first, (uint32_t *)fd);
+    if (rc) {
+        free(recs);
+        RP_OK(rc);
+    }
+    void *rd = NULL;
+    napi_value arr = new_typed(env, napi_float64_array, 15 * (size_t)cnt, 8, &rd);
+    for (uint32_t i = 0; i < cnt; i++) {
+        double *o = (double *)rd + 15 * (size_t)i;
+        const rp_sim_round_rec *r = recs + i;
+        o[0] = (double)r->round;
+        o[1] = (double)r->observers;
+        o[2] = (double)r->ck_min;
+        o[3] = (double)r->ck_max;
+        for (int k = 0; k < 4; k++) o[4 + k] = (double)r->pairs[k];
+        o[8] = (double)r->in_ring;
+        o[9] = (double)r->unmet;
+        o[10] = (double)r->false_faulty;
+        for (int k = 0; k < 4; k++) o[11 + k] = (double)r->stats[k];
+    }
+    free(recs);
+    napi_value out, v;
+    napi_create_object(env, &out);
+    napi_create_uint32(env, cnt, &v);
+    napi_set_named_property(env, out, "count", v);
+    napi_create_double(env, (double)first, &v);
+    napi_set_named_property(env, out, "firstRound", v);
+    napi_set_named_property(env, out, "recs", arr);
+    napi_set_named_property(env, out, "firstSeen", fs);
+    return out;
+}
+
 static napi_value js_sim_converged(napi_env env, napi_callback_info info) {
     ARGS(1);
     handle_t *h = get_handle(env, argv[0], 3);
@@ -1906,6 +1964,8 @@ static napi_value init(napi_env env, napi_value exports) {
         {"simCensus", NULL, js_sim_census, NULL, NULL, NULL, napi_default, NULL},
         {"simSides", NULL, js_sim_sides, NULL, NULL, NULL, napi_default, NULL},
         {"simSideSummary", NULL, js_sim_side_summary, NULL, NULL, NULL, napi_default, NULL},
+        {"simTimelineEnable", NULL, js_sim_timeline_enable, NULL, NULL, NULL, napi_default, NULL},
+        {"simTimelineRead", NULL, js_sim_timeline_read, NULL, NULL, NULL, napi_default, NULL},
     };
     napi_define_properties(env, exports, sizeof(later) / sizeof(later[0]), later);
     return exports;
