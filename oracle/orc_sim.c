@@ -1025,3 +1025,9 @@ void orc_sim_stats(const orc_sim *s, uint64_t *out4) {
 void orc_sim_piggyback(const orc_sim *s, uint32_t *out) {
     for (uint32_t v = 0; v < s->N; v++) out[v] = s->nodes[v].max_piggy;
 }
+
+void orc_sim_ring_members(const orc_sim *s, uint32_t v, uint8_t *in_ring) {
+    const node *nd = &s->nodes[v];
+    memset(in_ring, 1, s->N); /* a member without an entry is in its bootstrap state */
+    for (uint32_t i = 0; i < nd->ne; i++) in_ring[nd->e[i].addr] = nd->e[i].in_ring;
+}

@@ -98,6 +98,7 @@ def lib():
         L.orc_sim_event.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32]
         L.orc_sim_set_threads.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.orc_sim_piggyback.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        L.orc_sim_ring_members.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
         L.orc_js_pow.restype = ctypes.c_double
         L.orc_js_pow.argtypes = [ctypes.c_double, ctypes.c_double]
         L.orc_js_round.restype = ctypes.c_double
@@ -373,6 +374,12 @@ class Sim:
     def piggyback(self):
         out = np.empty(self.N, dtype=np.uint32)
         lib().orc_sim_piggyback(self.h, out.ctypes.data)
+        return out
+
+    def ring_members(self, v):
+        """uint8[N]: 1 for the members node v's hash ring holds."""
+        out = np.empty(self.N, dtype=np.uint8)
+        lib().orc_sim_ring_members(self.h, v, out.ctypes.data)
         return out
 
     def stats(self):

@@ -1,7 +1,7 @@
 """Regenerate the committed golden fixtures under tests/golden/ by running the REFERENCE
 JavaScript in this container (needs /root/reference and node; never runs on the GPU box).
 
-    python tests/golden/make_golden.py [ring] [membership] [sim] [simtiny]
+    python tests/golden/make_golden.py [ring] [membership] [sim] [simtiny] [simring]
 
 Inputs are built with the oracle's Philox / uuid stream (oracle/pyoracle.py); the reference's
 `farmhash` dependency is served by the oracle's N-API restatement (oracle/gen/farmhash_napi.c),
@@ -405,8 +405,66 @@ def make_sim():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def flap_cases():
+    """The flap family of tests/sim_ring_cases.py in the input schema of ref_sim.js."""
+    import sim_ring_cases as ringc
+    S = synth()
+    return [{"name": name, "family": "flap", "names": [S.c2_addr(i) for i in range(n)],
+             "inc0": [int(x) for x in S.c3_members(n)[2]], "dead": dead, "seed": ringc.SEED, "suspRounds": susp,
+             "now0": S.NOW0, "rounds": rounds, "views": [0, n - 1], "events": events}
+            for name, n, dead, rounds, susp, events in ringc.flap_cases()]
+
+
+def make_sim_ring():
+    """sim_ring_golden.json: which members the reference HashRing of every node holds after every
+    round, for every case of sim_tiny_golden.json and sim_net_golden.json (inputs regenerated from
+    the case modules, as those fixtures' generators do) and for the flap family."""
+    sys.path.insert(0, HERE)
+    import make_sim_net_golden as mn
+    groups = [("tiny", "ref_sim.js", sim_tiny_cases()), ("net", "ref_sim_net.js", mn.cases()),
+              ("flap", "ref_sim.js", flap_cases())]
+    fixture = {"generator": "tests/golden/make_golden.py simring (= make_sim_net_golden.py rings) + "
+                            "tests/sim_tiny_cases.py + tests/sim_net_cases.py + tests/sim_ring_cases.py + "
+                            "tests/golden/ref_sim.js + tests/golden/ref_sim_net.js",
+               "reference": "lib/ring/index.js hasServer() of each node's HashRing, kept by "
+                            "lib/on_membership_event.js (ringpop v10.9.6), in the runs of sim_golden.json",
+               "note": "per case: source = tiny (a case of sim_tiny_golden.json, by name), net (a case of "
+                       "sim_net_golden.json, by name; its two control cases are the tiny ones and are left out) or "
+                       "flap (inputs and the reference's checksums, maxPiggyback and fullSyncs stored here, in the "
+                       "schema of sim_tiny_golden.json); ringRuns = [[count, row], ...], count consecutive rounds "
+                       "with that row; row[v] = the servers of node v's ring after the round as a hex bit mask, bit "
+                       "i = node i; down nodes are recorded too (their state is kept)",
+               "cases": []}
+    seen = {}
+    for source, script, cases in groups:
+        outs = run_node(script, [dict(c, recordRings=True) for c in cases])
+        for c, o in zip(cases, outs):
+            assert len(o["rings"]) == c["rounds"] and all(len(row) == len(c["names"]) for row in o["rings"])
+            if c["name"] in seen:  # a control case of the net fixture: the tiny case again
+                assert c.get("family") == "control" and seen[c["name"]] == (o["rings"], o["rounds"]), c["name"]
+                continue
+            seen[c["name"]] = (o["rings"], o["rounds"])
+            f = {"name": c["name"], "source": source, "n": len(c["names"]), "rounds": c["rounds"]}
+            if source == "flap":
+                for k in ("family", "seed", "suspRounds", "now0", "views", "dead", "events"):
+                    f[k] = c[k]
+                f["checksumRuns"] = runs(o["rounds"])
+                f["maxPiggybackRuns"] = runs(o["maxPiggyback"])
+                f["fullSyncs"] = o["fullSyncs"]
+                f["finalViews"] = o["finalViews"]
+            f["ringRuns"] = runs(o["rings"])
+            fixture["cases"].append(f)
+    path = os.path.join(HERE, "sim_ring_golden.json")
+    with open(path, "w") as fh:
+        json.dump(fixture, fh, separators=(",", ":"))
+    print("wrote", path, os.path.getsize(path), "bytes,", len(fixture["cases"]), "cases")
+    assert os.path.getsize(path) < 1_000_000
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["ring", "membership", "sim"]
+    if "simring" in what:
+        make_sim_ring()
     if "ring" in what:
         make_ring()
     if "membership" in what:

@@ -2,7 +2,10 @@
 through the REFERENCE modules by tests/golden/ref_sim_net.js (needs the reference checkout and
 node, as make_golden.py does; never runs on the GPU box).
 
-    python tests/golden/make_sim_net_golden.py
+    python tests/golden/make_sim_net_golden.py [rings]
+
+`rings` instead writes tests/golden/sim_ring_golden.json (make_golden.py simring: every node's ring
+after every round, for these cases through ref_sim_net.js and for the tiny and flap cases).
 
 Outputs are data only: the cases and what the reference returned. Rerunning reproduces the
 committed file byte for byte."""
@@ -71,4 +74,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["rings"]:
+        mg.make_sim_ring()
+    else:
+        main()

@@ -24,7 +24,7 @@
 //
 // Reference code doing the work per node: lib/membership (Membership, Member, merge),
 // lib/gossip/dissemination.js, lib/gossip/suspicion.js, lib/membership/iterator.js,
-// lib/ring (HashRing, only for maxPiggybackCount), lib/on_membership_event.js (wiring).
+// lib/ring (HashRing: maxPiggybackCount, and its servers when c.recordRings), lib/on_membership_event.js (wiring).
 // The harness replaces only transport and time: TChannel ping/ping-req become synchronous
 // calls in the model's phase order (restating ping-sender.js / ping-req-sender.js /
 // server/protocol/ping*.js), setTimeout is a round-based virtual timer, Date.now() is
@@ -96,6 +96,16 @@ FakeRingpop.prototype.stat = function (type, key) { if (key === 'full-sync') { t
 
 function digits(n) { var d = 0; while (n) { d++; n = Math.floor(n / 10); } return d; }
 function wire(x) { return JSON.parse(JSON.stringify(x)); }
+// the servers of a node's HashRing among `names` as a bit mask in hex (bit i = names[i])
+function ringMask(rp, names) {
+    var hex = '';
+    for (var i = 0; i < names.length; i += 4) {
+        var nib = 0;
+        for (var k = 0; k < 4 && i + k < names.length; k++) { if (rp.ring.hasServer(names[i + k])) { nib |= 1 << k; } }
+        hex = nib.toString(16) + hex;
+    }
+    return hex;
+}
 
 var out = {cases: []};
 input.cases.forEach(function (c) {
@@ -163,7 +173,7 @@ input.cases.forEach(function (c) {
         if (side[v] !== side[j]) { br.unreachable++; }  // the cut decided it, or would have
         return live(j) && side[v] === side[j];
     }
-    var co = {name: c.name, rounds: [], maxPiggyback: [], sides: []};
+    var co = {name: c.name, rounds: [], maxPiggyback: [], rings: [], sides: []};
     // how often the case took each small-cluster branch (tests/golden/sim_tiny_golden.json)
     var br = {noTarget: 0, pingReq0: 0, pingReq1: 0, pingReq2: 0, helperDown: 0, join1: 0, join2: 0,
         leaveRedundant: 0, unreachable: 0};
@@ -302,6 +312,8 @@ input.cases.forEach(function (c) {
         co.rounds.push(cks);
         co.sides.push(side.slice());
         co.maxPiggyback.push(nodes.map(function (x) { return x.dissemination.maxPiggybackCount; }));
+        // c.recordRings: every node's ring after the round, down nodes too (their state is kept)
+        if (c.recordRings) { co.rings.push(nodes.map(function (x) { return ringMask(x, c.names); })); }
     }
     co.fullSyncs = nodes.reduce(function (a, x) { return a + x.fullSyncs; }, 0);
     co.finalViews = (c.views || []).map(function (v) {

@@ -25,9 +25,37 @@ def load_sim(name):
             for key, packed in (("checksums", "checksumRuns"), ("maxPiggyback", "maxPiggybackRuns")):
                 if packed in c:
                     c[key] = [row for count, row in c.pop(packed) for _ in range(count)]
-            assert len(c["checksums"]) == len(c["maxPiggyback"]) == c["rounds"]
+            if "checksums" in c or "ringRuns" not in c:  # (a ring case may name its source fixture instead)
+                assert len(c["checksums"]) == len(c["maxPiggyback"]) == c["rounds"]
         _SIM[name] = fixture
     return _SIM[name]
+
+
+_RING = {}
+
+
+def load_sim_ring():
+    """sim_ring_golden.json by case name, every case in the schema of its source fixture (a tiny or
+    net case takes its inputs and checksums from sim_tiny_golden.json / sim_net_golden.json, a flap
+    case holds its own), plus rings = uint8[rounds][n][n]: rings[r][v][i] = 1 when the reference
+    ring of node v held node i after round r. Parsed once per process; callers do not modify it."""
+    if not _RING:
+        import numpy as np
+
+        import sim_net_cases
+        src = {"tiny": {c["name"]: c for c in load_sim("sim_tiny_golden.json")["cases"]}, "net": sim_net_cases.load()}
+        for f in load_sim("sim_ring_golden.json")["cases"]:
+            c = dict(src[f["source"]][f["name"]], source=f["source"]) if f["source"] in src else dict(f)
+            assert (c["n"], c["rounds"]) == (f["n"], f["rounds"]), f["name"]
+            rows = [row for count, row in f["ringRuns"] for _ in range(count)]
+            assert len(rows) == c["rounds"] and all(len(row) == c["n"] for row in rows), f["name"]
+            bits = np.array([[[int(m, 16) >> i & 1 for i in range(c["n"])] for m in row] for row in rows],
+                            dtype=np.uint8)
+            assert all(int(m, 16) >> c["n"] == 0 for row in rows for m in row), f["name"]
+            c.pop("ringRuns", None)
+            c["rings"] = bits
+            _RING[c["name"]] = c
+    return _RING
 
 
 def hash_func(case):

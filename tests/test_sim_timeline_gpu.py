@@ -2,7 +2,8 @@
 §4.4c): one record of cluster-wide aggregates per round, appended on the device. Reference:
 tests/timeline_model.py fed from a twin handle stepped one round at a time (view(v),
 ring_members(v), checksums(), stats(); from 129 nodes on the counts come from census(), which
-test_sim_census_gpu.py pins). Bit-exact throughout.
+test_sim_ring_gpu.py pins at 127..513 nodes against the CPU oracle's rows, where it also compares
+the timeline at 129 and 513 nodes with the model fed from the oracle alone). Bit-exact throughout.
 
 sim_tiny_golden.json has no one-node case (rp_sim_create refuses n < 2), so the smallest clusters
 here are two of its two-node cases."""
