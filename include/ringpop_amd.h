@@ -782,6 +782,27 @@ int rp_sim_counters(rp_sim *s, uint64_t *out8);
 /* Node v's ring membership: in_ring[N] 0/1, what its ring holds (kept by the alive / faulty /
  * leave handler and the join's set handler, lib/on_membership_event.js). */
 int rp_sim_ring_members(rp_sim *s, uint32_t v, uint8_t *in_ring);
+/* Every local node's ring checksum (lib/ring/index.js:96-105 computeChecksum), out[the handle's
+ * nodes] in id order: farmhash32 of the names of the members node v's ring holds (the rows with
+ * rp_sim_ring_members' bit), in address order (Object.keys(servers).sort() of ASCII addresses),
+ * joined by ';' with no trailing separator. It is the value a forwarded request's head carries
+ * (lib/request-proxy/send.js:135-147) and the receiver compares with its own
+ * (lib/request-proxy/index.js:168-191), NOT the membership checksum of rp_sim_checksums: a suspect
+ * member stays in the ring, so views with different membership checksums can share a ring checksum.
+ * A ring that holds nobody gives hash32("") = 0xdc56d17a, computed on the host. A node that is
+ * down answers too: its ring is kept, as its rows are. On the handle's stream after the rounds
+ * queued so far, host output, synchronous; a sharded handle answers only at a round boundary
+ * (before stage 0), else RP_EINVAL; an empty shard writes nothing. Computed on demand: no round
+ * does anything for it. The call scans every node's deviation bitmap (only the status bytes of set
+ * bits are read, by the invariant rp_sim_census documents), describes each view by (absent members,
+ * their name bytes, a 64-bit order-free fingerprint of their ranks), and builds and hashes one
+ * string per class of equal views: a view whose description equals a lower-id view's is compared
+ * with it exactly, word by word, and copies its result only when the absent sets are equal, so a
+ * fingerprint collision costs a comparison and never a wrong checksum. RP_SIM_RCK_TWINS=0 (read
+ * per call; default on) builds every view. The strings are built in batches into a scratch the
+ * handle owns, of at most RP_SIM_RCK_BYTES bytes (read per call; default 256 MB, at least one
+ * string), and hashed by the launcher of rp_hash32_long_multi_dev. */
+int rp_sim_ring_checksums(rp_sim *s, uint32_t *out);
 /* Routing agreement of the handle's nodes: rp_ring_route_views_dev on the handle's stream, after
  * the rounds queued so far, with every local node's ring membership as one view of `ring`. ring
  * holds the members as servers, matched by name (a member the ring lacks is allowed nowhere; the

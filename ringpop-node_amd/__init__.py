@@ -152,6 +152,7 @@ SIGNATURES = {
     "rp_wire_decode": (_INT, [_P, _P, _P, _U32, _P, _U32, _P, _P, _P]),
     "rp_sim_counters": (_INT, [_P, _P]),
     "rp_sim_ring_members": (_INT, [_P, _U32, _P]),
+    "rp_sim_ring_checksums": (_INT, [_P, _P]),
     "rp_sim_routing": (_INT, [_P, _P, _P, _P, _U32, _U64, _P, _P, _P, _P, _P]),
     "rp_sim_routing_hashes": (_INT, [_P, _P, _P, _U64, _P, _P, _P, _P, _P]),
     "rp_sim_routing_share": (_INT, [_P, _P, _P, _P, _P, _P, _U32]),
@@ -1433,6 +1434,15 @@ class GossipSim:
         check(lib().rp_sim_ring_members(self._h, v, out.ctypes.data))
         return out.astype(bool)
 
+    def ring_checksums(self):
+        """Every node of this handle's ring checksum (uint32, in id order): farmhash32 of the
+        ';'-joined sorted names its ring holds (lib/ring/index.js computeChecksum), the value the
+        request proxy compares; nodes that are down included (rp_sim_ring_checksums)."""
+        out = np.empty(getattr(self, "NL", self.N), dtype=np.uint32)
+        if len(out):
+            check(lib().rp_sim_ring_checksums(self._h, out.ctypes.data))
+        return out
+
     def routing(self, ring, keys, truth=None):
         """Routing agreement of this handle's nodes on `ring` (a HashRing holding the members as
         servers, on the same device): {"wrong", "lost": uint64 per node, "key_wrong": uint32 per key,
@@ -1720,6 +1730,7 @@ class SimShard:
         return out
 
     ring_members = GossipSim.ring_members
+    ring_checksums = GossipSim.ring_checksums
     routing = GossipSim.routing
     routing_share = GossipSim.routingShare
     census = GossipSim.census
@@ -1816,6 +1827,10 @@ class ShardedGossipSim:
             if s.v0 <= v < s.v0 + s.NL:
                 return s.ring_members(v)
         raise IndexError(v)
+
+    def ring_checksums(self):
+        """Every node's ring checksum, gathered over the shards (GossipSim.ring_checksums)."""
+        return np.concatenate([s.ring_checksums() for s in self.shards])
 
     def default_truth(self):
         """bool[N]: the node is up (dead[] and the scenario's kills, revives and joins so far) and

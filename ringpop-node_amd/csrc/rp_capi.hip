@@ -17,7 +17,7 @@ extern "C" {
 
 const char* rp_last_error(void) { return rp::last_error(); }
 
-uint32_t rp_version(void) { return (1u << 16) | 7u; }
+uint32_t rp_version(void) { return (1u << 16) | 8u; }
 
 int rp_device_count(int* n) {
     return rp::guard([&] {

@@ -45,6 +45,7 @@
 
 #include "../../include/ringpop_amd.h"
 #include "rp_farmhash.h"
+#include "rp_hashlong.h"
 #include "rp_names.h"
 #include "rp_philox.h"
 #include "rp_prims.h"
@@ -3600,6 +3601,164 @@ __global__ __launch_bounds__(256) void k_census_finish(SimDev S, CensusDev C) {
     if (i < S.NL) C.o_behind[i] = C.obs[i] ? C.nlow[0] + C.acc[i] : 0u;
 }
 
+// ---- rp_sim_ring_checksums ----
+// A view's ring checksum string is the ring base (the pieces `name;` in address order, piece
+// offsets roff[N + 1]) with the pieces of its absent members deleted, minus the last byte. Absent
+// members are found as the census finds deviated rows: a clear deviation bit means the row is still
+// in the ring, so only the status bytes of set bits are read. k_rck_scan describes every view by
+// (absent count, absent piece bytes, an order-free 64-bit fingerprint of the absent ranks); the host
+// groups equal descriptions, k_rck_verify compares each candidate's absent set with its class's
+// lowest-id view word by word, and k_rck_build writes the strings of the views that remain
+// (representatives and failed candidates) for the long-string hash.
+constexpr uint32_t kRckThreads = 256;
+
+struct RckInfo {  // 16 bytes a view
+    uint32_t absent, bytes;
+    uint64_t fp;
+};
+
+struct RckDev {
+    const uint8_t* base;   // the ring base string
+    const uint32_t* roff;  // [N+1] piece offsets by address rank; roff[N] = the base's length
+    RckInfo* info;         // [NL]
+    const uint32_t* rep;   // [NL] the view each view is compared with (itself: not compared)
+    uint32_t* same;        // [NL] 1: the view's absent set equals its rep's
+    const uint32_t* list;  // the batch's views
+    uint32_t nlist;
+    uint8_t* slots;        // the batch's strings, `stride` apart
+    uint64_t stride;
+};
+
+// bit b set: the member at rank 32 w + b is not in view lv's ring
+__device__ __forceinline__ uint32_t rck_absent_word(const SimDev& S, uint32_t lv, uint32_t w) {
+    uint32_t bits = S.dev[(uint64_t)lv * S.W + w];
+    const uint32_t left = S.N - w * 32u;
+    if (left < 32u) bits &= (1u << left) - 1u;
+    const uint64_t row = (uint64_t)lv * S.N;
+    uint32_t out = 0;
+    while (bits) {
+        const uint32_t b = (uint32_t)__builtin_ctz(bits);
+        bits &= bits - 1;
+        if (!(S.st[row + S.sorted[w * 32u + b]] & IN_RING)) out |= 1u << b;
+    }
+    return out;
+}
+
+__device__ __forceinline__ uint64_t rck_mix(uint32_t k) {  // splitmix64's finisher of rank + 1
+    uint64_t z = ((uint64_t)k + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// one wave a local node
+__global__ __launch_bounds__(kRckThreads) void k_rck_scan(SimDev S, RckDev R) {
+    const uint32_t lv = blockIdx.x * (kRckThreads / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+    if (lv >= S.NL) return;
+    uint32_t cnt = 0, bytes = 0;
+    uint64_t fp = 0;
+    for (uint32_t w = lane; w < S.W; w += 64) {
+        uint32_t a = rck_absent_word(S, lv, w);
+        while (a) {
+            const uint32_t k = w * 32u + (uint32_t)__builtin_ctz(a);
+            a &= a - 1;
+            cnt++;
+            bytes += R.roff[k + 1] - R.roff[k];
+            fp += rck_mix(k);
+        }
+    }
+    for (int o = 32; o; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        bytes += __shfl_xor(bytes, o, 64);
+        fp += __shfl_xor(fp, o, 64);
+    }
+    if (lane == 0) R.info[lv] = RckInfo{cnt, bytes, fp};
+}
+
+// one wave a local node that has a candidate class: the exact comparison behind the fingerprint
+__global__ __launch_bounds__(kRckThreads) void k_rck_verify(SimDev S, RckDev R) {
+    const uint32_t lv = blockIdx.x * (kRckThreads / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
+    if (lv >= S.NL) return;
+    const uint32_t rv = R.rep[lv];
+    if (rv == lv || rv >= S.NL) {  // (wave-uniform)
+        if (lane == 0) R.same[lv] = 0;
+        return;
+    }
+    uint32_t diff = 0;
+    for (uint32_t w = lane; w < S.W; w += 64) diff |= rck_absent_word(S, lv, w) ^ rck_absent_word(S, rv, w);
+    const bool any = __ballot(diff != 0) != 0;
+    if (lane == 0) R.same[lv] = any ? 0u : 1u;
+}
+
+struct __attribute__((packed)) RckU16 {  // 16 bytes at any address
+    uint32_t x[4];
+};
+
+// One workgroup a listed view: its string into slot blockIdx.x. The words go by in chunks of one a
+// thread; a scan over the chunk gives every word the bytes deleted before it. A word without an
+// absent member is the base shifted by a constant and is copied by a wave with 16-byte stores; a
+// word with one is copied piece by piece, a lane each. The bytes a view writes are
+// [0, roff[N] - its absent bytes), inside the slot (stride >= roff[N] + 16).
+__global__ __launch_bounds__(kRckThreads) void k_rck_build(SimDev S, RckDev R) {
+    __shared__ uint32_t l_abs[kRckThreads], l_del[kRckThreads], l_scan[kRckThreads];
+    if (blockIdx.x >= R.nlist) return;
+    const uint32_t lv = R.list[blockIdx.x];
+    if (lv >= S.NL) return;
+    uint8_t* dst = R.slots + R.stride * blockIdx.x;
+    const uint32_t tid = threadIdx.x, wv = tid / 64, lane = tid & 63;
+    uint32_t carry = 0;
+    for (uint32_t c0 = 0; c0 < S.W; c0 += kRckThreads) {
+        const uint32_t w = c0 + tid;
+        const uint32_t a = w < S.W ? rck_absent_word(S, lv, w) : 0u;
+        uint32_t del = 0;
+        for (uint32_t m = a; m; m &= m - 1) {
+            const uint32_t k = w * 32u + (uint32_t)__builtin_ctz(m);
+            del += R.roff[k + 1] - R.roff[k];
+        }
+        l_abs[tid] = a;
+        l_scan[tid] = del;
+        __syncthreads();
+        for (uint32_t o = 1; o < kRckThreads; o <<= 1) {  // inclusive scan
+            const uint32_t add = tid >= o ? l_scan[tid - o] : 0u;
+            __syncthreads();
+            l_scan[tid] += add;
+            __syncthreads();
+        }
+        l_del[tid] = carry + l_scan[tid] - del;
+        const uint32_t chunk_del = l_scan[kRckThreads - 1];
+        __syncthreads();
+        for (uint32_t j = wv; j < kRckThreads && c0 + j < S.W; j += kRckThreads / 64) {
+            const uint32_t k0 = (c0 + j) * 32u, k1 = min(k0 + 32u, S.N);
+            const uint32_t am = l_abs[j], shift = l_del[j];
+            if (am == 0) {
+                const uint32_t s0 = R.roff[k0], len = R.roff[k1] - s0;
+                const uint8_t* sp = R.base + s0;
+                uint8_t* dp = dst + (s0 - shift);
+                const uint32_t head = min(len, (uint32_t)((0 - reinterpret_cast<uintptr_t>(dp)) & 15));
+                if (lane < head) dp[lane] = sp[lane];
+                const uint32_t nch = (len - head) / 16;
+                for (uint32_t c = lane; c < nch; c += 64)
+                {
+                    const RckU16 v = *reinterpret_cast<const RckU16*>(sp + head + 16 * c);
+                    *reinterpret_cast<uint4*>(dp + head + 16 * c) = uint4{v.x[0], v.x[1], v.x[2], v.x[3]};
+                }
+                const uint32_t done = head + 16 * nch;
+                if (lane < len - done) dp[done + lane] = sp[done + lane];
+            } else if (lane < k1 - k0 && !((am >> lane) & 1u)) {
+                uint32_t sh = shift;
+                for (uint32_t m = am & ((1u << lane) - 1u); m; m &= m - 1) {
+                    const uint32_t k = k0 + (uint32_t)__builtin_ctz(m);
+                    sh += R.roff[k + 1] - R.roff[k];
+                }
+                const uint32_t s0 = R.roff[k0 + lane], s1 = R.roff[k0 + lane + 1];
+                for (uint32_t b = s0; b < s1; b++) dst[b - sh] = R.base[b];
+            }
+        }
+        carry += chunk_del;
+        __syncthreads();
+    }
+}
+
 // ---- the timeline: one rp_sim_round_rec of aggregates per round ----
 // At the end of a round, after the refresh: k_tl_begin starts the round's slot, k_conv_ck counts
 // the observers and their checksum range into it, k_tl_count adds the observers' deviated rows to
@@ -3877,6 +4036,12 @@ struct Sim {
     DevBuf<uint32_t> cs_u32;
     DevBuf<int64_t> cs_i64;
     std::vector<uint8_t> cs_obs;
+    // rp_sim_ring_checksums: the ring base and its piece offsets (built at the first call), the
+    // per-view descriptions, twin classes and batch lists, and the batch's string slots and meta
+    DevBuf<uint8_t> rck_base, rck_slots;
+    DevBuf<uint32_t> rck_roff, rck_u32, rck_meta;
+    DevBuf<RckInfo> rck_info;
+    uint32_t rck_len = 0;  // the ring base's length (0: not built yet)
 
     uint32_t cus = 0;  // compute units of the device, at least 1 (first use)
     uint32_t cu() {
@@ -5213,6 +5378,132 @@ int rp_sim_census(rp_sim* s, const uint8_t* observe, const int64_t* max_ref, uin
         if (behind) RP_HIP(hipMemcpyAsync(behind, C.o_behind, 4ull * NL, hipMemcpyDeviceToHost, S.st));
         RP_HIP(hipStreamSynchronize(S.st));
     });
+}
+
+// The ring base of the handle's members, built at the first call: the pieces `name;` in address
+// order and their offsets.
+static void sim_rck_base(rp::Sim& S) {
+    if (S.rck_len) return;
+    const uint32_t N = S.N;
+    std::vector<uint32_t> sorted(N), roff(N + 1ull);
+    RP_HIP(hipMemcpyAsync(sorted.data(), S.nt.sorted.p, 4ull * N, hipMemcpyDeviceToHost, S.st));
+    RP_HIP(hipStreamSynchronize(S.st));
+    RP_REQUIRE(S.nt.h_bytes.size() + N < 0xFFFFFF00ull, "sim_ring_checksums: ring string past 4 GB");
+    std::vector<uint8_t> base;
+    base.reserve(S.nt.h_bytes.size() + N + 16);
+    for (uint32_t k = 0; k < N; k++) {
+        const uint32_t a = sorted[k];
+        roff[k] = (uint32_t)base.size();
+        base.insert(base.end(), S.nt.h_bytes.begin() + (long)S.nt.h_noff[a], S.nt.h_bytes.begin() + (long)S.nt.h_noff[a + 1]);
+        base.push_back(';');
+    }
+    roff[N] = (uint32_t)base.size();
+    S.rck_base.reserve(base.size() + 16);
+    S.rck_roff.reserve(N + 1ull);
+    RP_HIP(hipMemcpyAsync(S.rck_base.p, base.data(), base.size(), hipMemcpyHostToDevice, S.st));
+    RP_HIP(hipMemcpyAsync(S.rck_roff.p, roff.data(), 4ull * (N + 1), hipMemcpyHostToDevice, S.st));
+    RP_HIP(hipStreamSynchronize(S.st));
+    S.rck_len = roff[N];
+}
+
+// Every local node's ring checksum into out[NL] (host), on the handle's stream after the queued
+// rounds; returns with the stream idle.
+static void sim_ring_checksums(rp::Sim& S, uint32_t* out) {
+    RP_REQUIRE(S.G == 1 || S.next_stage == 0,
+               "sim_ring_checksums: a sharded handle answers at a round boundary (before stage 0)");
+    const uint32_t N = S.N, NL = S.NL;
+    if (NL == 0) return;
+    RP_REQUIRE(out, "sim_ring_checksums: null output");
+    RP_HIP(hipSetDevice(S.device));
+    sim_rck_base(S);
+    const char* tw = getenv("RP_SIM_RCK_TWINS");
+    const bool twins = !(tw && *tw == '0');
+    const uint64_t stride = ((uint64_t)S.rck_len + 16 + 15) & ~15ull;
+    const uint32_t per = (uint32_t)std::min<uint64_t>(NL, std::max<uint64_t>(1, env_u64("RP_SIM_RCK_BYTES", 256ull << 20) / stride));
+    S.rck_info.reserve(NL);
+    S.rck_u32.reserve(3ull * NL);  // rep | same | list
+    S.rck_slots.reserve((uint64_t)per * stride);
+    S.rck_meta.reserve(4ull * per);
+    rp::RckDev R{};
+    R.base = S.rck_base.p;
+    R.roff = S.rck_roff.p;
+    R.info = S.rck_info.p;
+    R.rep = S.rck_u32.p;
+    R.same = S.rck_u32.p + NL;
+    R.slots = S.rck_slots.p;
+    R.stride = stride;
+    const unsigned waves = (NL + rp::kRckThreads / 64 - 1) / (rp::kRckThreads / 64);
+    hipLaunchKernelGGL(rp::k_rck_scan, dim3(waves), dim3(rp::kRckThreads), 0, S.st, S.d, R);
+    RP_HIP(hipGetLastError());
+    std::vector<rp::RckInfo> info(NL);
+    RP_HIP(hipMemcpyAsync(info.data(), R.info, sizeof(rp::RckInfo) * NL, hipMemcpyDeviceToHost, S.st));
+    RP_HIP(hipStreamSynchronize(S.st));
+    // twin classes: equal descriptions are candidates of their lowest-id view; only an exact match
+    // of the absent sets keeps a candidate in its class
+    std::vector<uint32_t> rep(NL);
+    for (uint32_t lv = 0; lv < NL; lv++) rep[lv] = lv;
+    if (twins && NL > 1) {
+        std::vector<uint32_t> ord(rep);
+        std::sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
+            const rp::RckInfo &a = info[x], &b = info[y];
+            if (a.absent != b.absent) return a.absent < b.absent;
+            if (a.bytes != b.bytes) return a.bytes < b.bytes;
+            if (a.fp != b.fp) return a.fp < b.fp;
+            return x < y;
+        });
+        bool any = false;
+        for (uint32_t i = 1, head = 0; i < NL; i++) {
+            const rp::RckInfo &a = info[ord[head]], &b = info[ord[i]];
+            if (a.absent == b.absent && a.bytes == b.bytes && a.fp == b.fp) {
+                rep[ord[i]] = ord[head];
+                any = true;
+            } else {
+                head = i;
+            }
+        }
+        if (any) {
+            std::vector<uint32_t> same(NL);
+            RP_HIP(hipMemcpyAsync(S.rck_u32.p, rep.data(), 4ull * NL, hipMemcpyHostToDevice, S.st));
+            hipLaunchKernelGGL(rp::k_rck_verify, dim3(waves), dim3(rp::kRckThreads), 0, S.st, S.d, R);
+            RP_HIP(hipGetLastError());
+            RP_HIP(hipMemcpyAsync(same.data(), R.same, 4ull * NL, hipMemcpyDeviceToHost, S.st));
+            RP_HIP(hipStreamSynchronize(S.st));
+            for (uint32_t lv = 0; lv < NL; lv++)
+                if (rep[lv] != lv && !same[lv]) rep[lv] = lv;  // a fingerprint collision: built on its own
+        }
+    }
+    const uint32_t empty = rp_hash32("", 0);  // computeChecksum of no servers
+    std::vector<uint32_t> list;
+    for (uint32_t lv = 0; lv < NL; lv++) {
+        if (rep[lv] != lv) continue;
+        if (info[lv].absent >= N) out[lv] = empty;
+        else list.push_back(lv);
+    }
+    if (!list.empty()) RP_HIP(hipMemcpyAsync(S.rck_u32.p + 2ull * NL, list.data(), 4ull * list.size(), hipMemcpyHostToDevice, S.st));
+    std::vector<uint32_t> meta(4ull * per);
+    for (size_t b0 = 0; b0 < list.size(); b0 += per) {
+        const uint32_t nb = (uint32_t)std::min<size_t>(per, list.size() - b0);
+        for (uint32_t i = 0; i < nb; i++) {
+            meta[4 * i] = S.rck_len - info[list[b0 + i]].bytes;  // piece total = length + 1
+            meta[4 * i + 1] = 1;
+            meta[4 * i + 2] = meta[4 * i + 3] = 0;
+        }
+        RP_HIP(hipMemcpyAsync(S.rck_meta.p, meta.data(), 16ull * nb, hipMemcpyHostToDevice, S.st));
+        R.list = S.rck_u32.p + 2ull * NL + b0;
+        R.nlist = nb;
+        hipLaunchKernelGGL(rp::k_rck_build, dim3(nb), dim3(rp::kRckThreads), 0, S.st, S.d, R);
+        RP_HIP(hipGetLastError());
+        rp::hash_long_multi(S.rck_slots.p, stride, nb, S.rck_meta.p, S.st);
+        RP_HIP(hipMemcpyAsync(meta.data(), S.rck_meta.p, 16ull * nb, hipMemcpyDeviceToHost, S.st));
+        RP_HIP(hipStreamSynchronize(S.st));
+        for (uint32_t i = 0; i < nb; i++) out[list[b0 + i]] = meta[4 * i + 2];
+    }
+    for (uint32_t lv = 0; lv < NL; lv++)
+        if (rep[lv] != lv) out[lv] = out[rep[lv]];
+}
+
+int rp_sim_ring_checksums(rp_sim* s, uint32_t* out) {
+    return guard([&] { sim_ring_checksums(SM(s), out); });
 }
 
 int rp_sim_sides(rp_sim* s, uint8_t* side) {
