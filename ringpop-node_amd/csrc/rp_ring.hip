@@ -1200,10 +1200,60 @@ __global__ __launch_bounds__(kLkThreads) __attribute__((amdgpu_waves_per_eu(4)))
 // LDS: rows (12 B a key) over the key slice (<= 18 KB per 256 threads) and the ordered (h, kk)
 // pairs (8 B a key), both dead before the rows are written; + the 16-bit bin counters (two to
 // a word) and the per-wave lists.
+//
+// Two kernels run the same tile body. Strided (k_lookupn_sorted): workgroup b takes tiles b,
+// b + grid, ... Ticketed (k_lookupn_sorted_ticket, launched at 256 threads; RP_LOOKUP_TICKET):
+// the strided kernel's body with the marked additions, as a kernel of its own because the body
+// moved into a function both inline is scheduled differently by the compiler, and the strided
+// kernels' code is to stay what was measured (tools/cmp_device_asm.py). There
+// the grid is what is resident; a workgroup starts on tile blockIdx.x and draws every later one,
+// grid + a ticket, from the device counter tick[0]. Lane 0 draws with one relaxed agent-scope
+// atomicAdd at the top of the tile before, keeps the ticket in a register under that tile's key
+// stream, hands it to the other lanes through LDS across barriers the loop has anyway, and a tile
+// index >= ntiles ends the workgroup before anything is written for it. No wave ever waits on
+// another workgroup, so the launch drains however few workgroups are resident. tick[1] counts
+// the workgroups that have left: the last one puts both words back to 0 (every draw of every
+// workgroup has returned by then), so a call costs no memset and no extra launch.
+// Stagger (RP_LOOKUP_STAGGER): before its first tile the workgroup in resident slot
+// j = (blockIdx.x / slot_div) % 4 of its CU sleeps j * stagger s_sleep(16) (a count fixed at
+// launch, never a wait on memory), so a CU's workgroups do not run their phases in step.
 #ifdef RP_LK_PROF
 __device__ unsigned long long g_sk_prof[10];
+#define RP_LK_TL
+#endif
+// -DRP_LK_TL alone: the timeline without the phase counters, whose waits slow the kernel by a fifth.
+#ifdef RP_LK_TL
+// The launch's timeline (tools/lk_timeline.py; s_memrealtime, 100 MHz): per workgroup its start
+// and end stamps and HW_ID / XCC_ID, per tile its end stamp and workgroup. Nothing reads these
+// on the device.
+constexpr uint32_t kTlMaxWg = 16384, kTlMaxTiles = 32768;
+__device__ unsigned long long g_tl_wg[2 * kTlMaxWg];
+__device__ uint32_t g_tl_hw[2 * kTlMaxWg];
+__device__ unsigned long long g_tl_tile[kTlMaxTiles];
+__device__ uint32_t g_tl_tile_wg[kTlMaxTiles];
+#define RP_TL_BEGIN()                                                                  \
+    if (threadIdx.x == 0 && blockIdx.x < kTlMaxWg) {                                   \
+        g_tl_wg[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();                    \
+        g_tl_hw[2 * blockIdx.x] = __builtin_amdgcn_s_getreg(4 | (31 << 11));      /* HW_ID */  \
+        g_tl_hw[2 * blockIdx.x + 1] = __builtin_amdgcn_s_getreg(20 | (31 << 11)); /* XCC_ID */ \
+    }
+#define RP_TL_TILE(t)                                      \
+    if (threadIdx.x == 0 && (t) < kTlMaxTiles) {           \
+        g_tl_tile[t] = __builtin_amdgcn_s_memrealtime();   \
+        g_tl_tile_wg[t] = blockIdx.x;                      \
+    }
+#define RP_TL_END() \
+    if (threadIdx.x == 0 && blockIdx.x < kTlMaxWg) g_tl_wg[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime()
+#else
+#define RP_TL_BEGIN()
+#define RP_TL_TILE(t)
+#define RP_TL_END()
 #endif
 constexpr int kSortDefault = 256;  // RP_LOOKUP_SORT when unset (0: the lean kernel; profiles/LOG.md)
+constexpr bool kTicketDefault = true;   // RP_LOOKUP_TICKET when unset (0.810 against 0.834 ms strided; profiles/LOG.md)
+constexpr int kStaggerDefault = 0;      // RP_LOOKUP_STAGGER when unset, sixteenths of a tile time (1/8, 1/4: no gain; 1/2: slower)
+constexpr uint64_t kSortedTileUs = 25;  // a 2,048-key tile of a resident workgroup at C2 (0.2 ms / 8 tiles)
+constexpr uint32_t kStaggerSlots = 4;   // resident workgroups a CU the stagger tells apart
 
 template <int THREADS, int NEED>
 __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_lookupn_sorted(
@@ -1232,6 +1282,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
 #ifdef RP_LK_PROF
     uint64_t pa[6] = {0, 0, 0, 0, 0, 0}, ntl = 0;
 #endif
+    RP_TL_BEGIN();
     if (tid < CW) bins[tid] = 0;
     if (tid < SUB) nslow_sub[tid] = 0;
     for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
@@ -1331,6 +1382,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         pa[5] += t6 - t5;
         ntl += 1;
 #endif
+        RP_TL_TILE(t);
     }
 #ifdef RP_LK_PROF
     if (lane == 0) {
@@ -1338,6 +1390,174 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) vo
         atomicAdd(&g_sk_prof[6], (unsigned long long)ntl);
     }
 #endif
+    RP_TL_END();
+}
+
+// The ticketed form (see above): k_lookupn_sorted's body, plus the stagger before the loop, the
+// draw at the top of a tile, the hand-over of the ticket through next_tile, and the exit count.
+// tick: Ring::tick. stagger: s_sleep(16) steps per resident slot (0: none). slot_div: blocks per
+// resident slot (the CU count).
+template <int THREADS, int NEED>
+__global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(4))) void k_lookupn_sorted_ticket(
+    const uint8_t* __restrict__ keys, uint64_t ntiles, CompactView cv, uint32_t* __restrict__ out,
+    uint8_t* __restrict__ counts, uint32_t* __restrict__ slow_list, uint32_t* __restrict__ slow_cnt,
+    uint32_t* __restrict__ tick, uint32_t stagger, uint32_t slot_div) {
+    constexpr int LEN = 36, W4 = LEN / 4, KPL = 8, HS = 4;
+    constexpr int TK = THREADS * KPL;
+    constexpr int NW = THREADS / 64;
+    constexpr int SUB = TK / 2048;  // the lean kernel's logical tiles in one of these
+    constexpr int SK = TK * W4 / HS, SO = TK * NEED;
+    constexpr int BINS = THREADS;                 // 256 | 512 | 1024 bins on the top hash bits
+    constexpr int BSH = 32 - (BINS == 256 ? 8 : BINS == 512 ? 9 : 10);
+    constexpr int CW = BINS / 2;                  // counter words: two 16-bit bins each
+    constexpr int WPL = CW / 64;                  // counter words a lane of the scanning wave takes
+    static_assert(THREADS == 256 || THREADS == 512 || THREADS == 1024, "whole 2,048-key logical tiles, 13-bit slots, 16-bit bin counters");
+    static_assert(2 * TK <= SO && SK <= SO, "the ordered pairs and the key slice fit under the rows");
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SO];
+    __shared__ uint32_t ag[NW][3][kLkAG];  // per-wave second-window list (LkStages::resolve)
+    __shared__ uint32_t bins[CW];
+    __shared__ uint32_t nslow_sub[SUB];
+    __shared__ uint32_t next_tile;  // the drawn ticket, from lane 0 to the workgroup
+    uint32_t* const sk = lds;  // a slice of 128 keys a wave
+    uint32_t* const so = lds;
+    u32x2* const pairs = reinterpret_cast<u32x2*>(lds);  // TK x (h, kk)
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const LkStages<NEED, 13> lk(cv);
+#ifdef RP_LK_PROF
+    uint64_t pa[6] = {0, 0, 0, 0, 0, 0}, ntl = 0;
+#endif
+    RP_TL_BEGIN();
+    if (tid < CW) bins[tid] = 0;
+    if (tid < SUB) nslow_sub[tid] = 0;
+    const uint32_t naps = ((blockIdx.x / slot_div) % kStaggerSlots) * stagger;
+    for (uint32_t i = 0; i < naps; i++) __builtin_amdgcn_s_sleep(16);
+    uint64_t nxt = 0;
+    uint32_t zero;
+    asm("v_mov_b32 %0, 0" : "=v"(zero));
+    for (uint64_t t = blockIdx.x; t < ntiles; t = nxt) {
+        const uint64_t base = t * TK;
+        uint32_t h[KPL], kk[KPL];
+        // the next tile's ticket: the trip runs under this tile's key stream
+        // (the zero the compiler cannot see keeps the address per-lane: with a uniform address
+        // the add is rewritten as a wave-wide one whose result is broadcast, and waited for, here)
+        uint32_t drawn = 0;
+        if (tid == 0) drawn = __hip_atomic_fetch_add(tick + zero, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        LK_T(t0, tid);
+        // each wave stages and hashes its own 512 keys (tile slots wv * 512 + lane + 64 k): no
+        // workgroup barrier until the counts
+        lk_key_stage<64, KPL, HS, true>(keys + (base + (uint64_t)wv * 512) * LEN, sk + wv * (SK / NW), lane, h, [] {}, [] {});
+        LK_T(t1, h[KPL - 1]);
+        // rank in the bin: one LDS atomic per key (its half of the counter word)
+        uint32_t rank[KPL];
+#pragma unroll
+        for (int k = 0; k < KPL; k++) {
+            const uint32_t b = h[k] >> BSH, sh = (b & 1u) * 16u;
+            rank[k] = (atomicAdd(&bins[b >> 1], 1u << sh) >> sh) & 0xFFFFu;
+        }
+        if (tid == 0) next_tile = drawn;  // read after the barrier that ends the trips below
+        __syncthreads();  // the counts are whole, and the last key slice is hashed
+        if (wv == 0) {  // exclusive scan of the bin counts in place, by one wave: bin starts
+            uint32_t c[WPL], sum = 0;
+#pragma unroll
+            for (int i = 0; i < WPL; i++) {
+                c[i] = bins[lane * WPL + i];
+                sum += (c[i] & 0xFFFFu) + (c[i] >> 16);
+            }
+            uint32_t x = sum;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t y = __shfl_up(x, o, 64);
+                if (lane >= o) x += y;
+            }
+            uint32_t run = x - sum;
+#pragma unroll
+            for (int i = 0; i < WPL; i++) {
+                const uint32_t a = run, b = run + (c[i] & 0xFFFFu);
+                run = b + (c[i] >> 16);
+                bins[lane * WPL + i] = a | (b << 16);  // starts <= TK <= 8192
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < KPL; k++) {
+            const uint32_t b = h[k] >> BSH, sh = (b & 1u) * 16u;
+            const uint32_t slot = ((bins[b >> 1] >> sh) & 0xFFFFu) + rank[k];
+            pairs[slot] = u32x2{h[k], (uint32_t)(wv * 512 + lane + 64 * k)};
+        }
+        __syncthreads();
+        // lane tid takes slots tid + k THREADS: a wave instruction holds 64 consecutive slots
+#pragma unroll
+        for (int k = 0; k < KPL; k++) {
+            const u32x2 p = pairs[tid + k * THREADS];
+            h[k] = p.x;
+            kk[k] = p.y;
+        }
+        if (tid < CW) bins[tid] = 0;  // for the next tile (the starts were read before the barrier above)
+        if (tid < SUB) nslow_sub[tid] = 0;
+        LK_T(t2, kk[KPL - 1]);
+        __syncthreads();  // the pairs are dead: the rows take their place
+        uint32_t nag = 0;  // wave-uniform length of this wave's list
+        uint8_t* const cnt_tile = counts ? counts + base : nullptr;
+        auto defer = [&](uint32_t k) {  // to the list of the key's 2,048-key logical tile
+            const uint32_t s = k >> 11;
+            const uint32_t sp = atomicAdd(&nslow_sub[s], 1u);
+            if (sp < kSlowPerTile) slow_list[(t * SUB + s) * kSlowPerTile + sp] = k & 2047u;
+        };
+        u32x2 rec[KPL];
+#pragma unroll
+        for (int k = 0; k < KPL; k++) rec[k] = lk.index_rec(h[k]);
+        uint32_t lo[KPL], bc[KPL], ws[KPL];
+        u32x4 win[KPL];
+#pragma unroll
+        for (int k = 0; k < KPL; k++) win[k] = lk.window(h[k], rec[k], lo[k], bc[k], ws[k]);
+        LK_T(t3, lo[KPL - 1]);
+#pragma unroll
+        for (int k = 0; k < KPL; k++) lk.resolve(win[k], h[k], lo[k], bc[k], ws[k], kk[k], nag, ag[wv], so, cnt_tile, defer);
+        LK_T(t4, nag);
+        // second windows, one listed key per lane (the list is this wave's own LDS rows)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        for (uint32_t j = lane; j < (nag < kLkAG ? nag : kLkAG); j += 64)
+            lk.finish2(lk.load16(ag[wv][0][j]), ag[wv][1][j], ag[wv][2][j], so, cnt_tile, defer);
+        LK_T(t5a, nag);
+        __syncthreads();
+        LK_T(t5, tid);
+        // (the word is next written before the next tile's first barrier, past the barrier below)
+        nxt = (uint64_t)gridDim.x + next_tile;
+        if (tid < SUB) slow_cnt[t * SUB + tid] = nslow_sub[tid];
+        u32x4* d4 = reinterpret_cast<u32x4*>(out + base * NEED);
+        const u32x4* s4 = reinterpret_cast<const u32x4*>(so);
+#pragma unroll
+        for (int k = tid; k < TK * NEED / 4; k += THREADS) __builtin_nontemporal_store(s4[k], d4 + k);
+        __syncthreads();
+#ifdef RP_LK_PROF
+        LK_T(t6, tid);
+        pa[0] += t1 - t0;
+        pa[1] += t2 - t1;
+        pa[2] += t3 - t2;
+        pa[3] += t4 - t3;
+        pa[4] += t5a - t4;
+        pa[5] += t6 - t5;
+        ntl += 1;
+#endif
+        RP_TL_TILE(t);
+    }
+#ifdef RP_LK_PROF
+    if (lane == 0) {
+        for (int i = 0; i < 6; i++) atomicAdd(&g_sk_prof[i], (unsigned long long)pa[i]);
+        atomicAdd(&g_sk_prof[6], (unsigned long long)ntl);
+    }
+#endif
+    RP_TL_END();
+    // Lane 0's own last draw has returned (its value ended the loop), as has every draw of a
+    // workgroup whose exit is counted: the workgroup that counts the last exit finds no draw in
+    // flight and puts the two words back for the next launch.
+    if (tid == 0) {
+        const uint32_t left = __hip_atomic_fetch_add(tick + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (left + 1u == gridDim.x) {
+            __hip_atomic_store(tick, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(tick + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // ---- The wave-specialised lean kernel (round 6, A/B: RP_LOOKUP_WS). The lean kernel's waves run
@@ -2731,8 +2951,20 @@ struct LookupKnobs {
     int kpl;       // its number; each path maps it to the tiles it has
     // RP_LOOKUP_SORT: threads of the sorted-tile kernel, 0 = off (unset: kSortDefault)
     int sort_t;
-    // RP_LOOKUP_GRID: workgroups of the sorted, lean and compact kernels (0: unset)
+    // RP_LOOKUP_GRID: workgroups of the sorted, lean and compact kernels (0: unset); the sorted
+    // kernel it names is the strided one
     uint64_t grid;
+    // RP_LOOKUP_TICKET: the 256-thread sorted tiles by ticket on a resident grid (1) or strided
+    // over RP_LOOKUP_GRID's default (0); -1: unset (kTicketDefault)
+    int ticket;
+    // RP_LOOKUP_STAGGER: the ticketed form's start stagger, sixteenths of a tile time between the
+    // resident workgroups of a CU (0: off; -1: unset, kStaggerDefault)
+    int stagger;
+    // RP_LOOKUP_TICKET_GRID: the ticketed form's workgroups, not capped at the tile count (tests
+    // only; 0: unset, what is resident)
+    uint64_t ticket_grid;
+    // RP_LK_TL_DUMP: the file a -DRP_LK_TL (or -DRP_LK_PROF) build writes the sorted launch's timeline to
+    const char* tl_dump;
     // RP_LOOKUP_LEAN=0: the round-1 compact kernel, not the lean one
     bool lean_set;  // set, whatever the value: no sorted kernel
     bool lean;
@@ -2759,7 +2991,8 @@ static LookupKnobs lookup_knobs() {
     const auto is0 = [](const char* v) { return v && !strcmp(v, "0"); };
     const char *lay = getenv("RP_RING_LAYOUT"), *abl = getenv("RP_LOOKUP_ABLATE"), *lds = getenv("RP_LOOKUP_LDS"),
                *ws = getenv("RP_LOOKUP_WS"), *kpl = getenv("RP_LOOKUP_KPL"), *sort = getenv("RP_LOOKUP_SORT"),
-               *lean = getenv("RP_LOOKUP_LEAN"), *half = getenv("RP_LOOKUP_HALF"), *stg = getenv("RP_LOOKUP_STG");
+               *lean = getenv("RP_LOOKUP_LEAN"), *half = getenv("RP_LOOKUP_HALF"), *stg = getenv("RP_LOOKUP_STG"),
+               *tick = getenv("RP_LOOKUP_TICKET"), *stag = getenv("RP_LOOKUP_STAGGER");
     LookupKnobs k;
     k.wide = getenv_flag("RP_RING_WIDE");
     k.layout_packed = lay && !strcmp(lay, "packed");
@@ -2781,6 +3014,10 @@ static LookupKnobs lookup_knobs() {
     k.kpl = num(kpl);
     k.sort_t = sort ? atoi(sort) : kSortDefault;
     k.grid = env_pos("RP_LOOKUP_GRID", 0);
+    k.ticket = tick ? (is0(tick) ? 0 : 1) : -1;
+    k.stagger = stag ? std::min(std::max(atoi(stag), 0), 64) : -1;
+    k.ticket_grid = env_pos("RP_LOOKUP_TICKET_GRID", 0);
+    k.tl_dump = getenv("RP_LK_TL_DUMP");
     k.lean_set = lean != nullptr;
     k.lean = !is0(lean);
     k.half_set = half != nullptr;
@@ -2815,6 +3052,12 @@ struct Ring {
     // packed lookup layout (valid while every interned id < 2^16)
     DevBuf<uint32_t> ent, pbstart;
     DevBuf<uint32_t> slow, nslow;  // deferred keys of the probe / compact kernels
+    // The ticketed sorted tiles' counters: [0] tickets drawn, [1] workgroups that have left. Zeroed
+    // once, when reserved; the last workgroup of every launch leaves both at 0. Like slow and
+    // nslow they belong to one batch lookup at a time: a handle's lookups must not overlap on the
+    // device (two streams without an order between them), or two launches share the tickets.
+    DevBuf<uint32_t> tick;
+    int ticket_per_cu = 0;  // k_lookupn_sorted_ticket<256, 3>'s workgroups a CU (0: not asked yet)
     bool packed = false;
     uint32_t pbits = 16;
     // compact lookup layout (the C2 hot path; valid while every interned id < 2^16)
@@ -3342,11 +3585,40 @@ static void lookupn_compact(Ring& r, const LookupKnobs& k, const Batch36& b, con
     const uint64_t ntiles = (n - s0) / TK, done = s0 + ntiles * TK;
     r.slow.reserve((t0 + ntiles) * kSlowPerTile + 1);
     r.nslow.reserve(t0 + ntiles + 1);
-    if (stiles) {
+    // The 256-thread tiles by ticket (RP_LOOKUP_TICKET; an explicit RP_LOOKUP_GRID names the
+    // strided kernel): the grid is what is resident, the CUs times the workgroups a CU of the
+    // occupancy query, capped at the tile count.
+    const bool ticket = stiles && sort_t == 256 && !k.grid && (k.ticket < 0 ? kTicketDefault : k.ticket == 1);
+    unsigned sg = 0;
+    int stag16 = 0;
+    if (ticket) {
+        if (!r.tick.p) {
+            r.tick.reserve(2);
+            RP_HIP(hipMemsetAsync(r.tick.p, 0, 2 * sizeof(uint32_t), st));
+            RP_HIP(hipStreamSynchronize(st));  // once a handle: later calls may come on other streams
+        }
+        if (!r.ticket_per_cu) {
+            int nbl = 0;
+            RP_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbl, reinterpret_cast<const void*>(k_lookupn_sorted_ticket<256, 3>), 256, 0));
+            r.ticket_per_cu = std::max(nbl, 1);
+        }
+        const uint64_t cus = (uint64_t)cu_count(r.device);
+        sg = (unsigned)(k.ticket_grid ? std::min<uint64_t>(k.ticket_grid, 1u << 20) : std::min<uint64_t>(cus * (uint64_t)r.ticket_per_cu, stiles));
+        // the stagger in s_sleep(16) = 1,024 clocks a step: stag16 / 16 of a tile time (kSortedTileUs)
+        stag16 = k.stagger < 0 ? kStaggerDefault : k.stagger;
+        int khz = 0;
+        if (stag16) (void)hipDeviceGetAttribute(&khz, hipDeviceAttributeClockRate, r.device);
+        const uint32_t naps = (uint32_t)((uint64_t)stag16 * kSortedTileUs * (uint64_t)(khz > 0 ? khz / 1000 : 2400) / (16u * 1024u));
+        // slot j of a CU: workgroups are dealt over the CUs before a CU gets its next one
+        // (profiles/ticket_tiles/), so j = blockIdx.x / CUs
+        hipLaunchKernelGGL((k_lookupn_sorted_ticket<256, 3>), dim3(sg), dim3(256), 0, st, b.keys, stiles, cv, b.out, b.counts,
+                           r.slow.p, r.nslow.p, r.tick.p, naps, (uint32_t)cus);
+        RP_HIP(hipGetLastError());
+    } else if (stiles) {
         // workgroups, tiles strided over them (2^26 C2 keys, profiles/sorted_tiles/grid_sweep.txt):
         // 256 threads 0.842 ms at 4096 (2048: 0.877, 8192: 0.845, 12288: 0.850); 512 threads 0.890
         // at 8192 (1024-4096: 0.93-0.95); 1024 threads 0.997 at 512-1024. RP_LOOKUP_GRID overrides (A/B).
-        const unsigned sg = grid_for(stiles, 1, (unsigned)(k.grid ? k.grid : sort_t == 256 ? 4096u : sort_t == 512 ? 8192u : 1024u));
+        sg = grid_for(stiles, 1, (unsigned)(k.grid ? k.grid : sort_t == 256 ? 4096u : sort_t == 512 ? 8192u : 1024u));
         const auto sorted = [&](auto kern) {
             hipLaunchKernelGGL(kern, dim3(sg), dim3(sort_t), 0, st, b.keys, stiles, cv, b.out, b.counts, r.slow.p, r.nslow.p);
         };
@@ -3430,11 +3702,32 @@ static void lookupn_compact(Ring& r, const LookupKnobs& k, const Batch36& b, con
         }
     }
 #endif
+#ifdef RP_LK_TL
+    if (k.tl_dump && stiles) {  // the sorted launch's timeline, as text (tools/lk_timeline.py reads it)
+        const uint32_t nwg = std::min<uint32_t>(sg, kTlMaxWg), nt = (uint32_t)std::min<uint64_t>(stiles, kTlMaxTiles);
+        std::vector<unsigned long long> wg(2 * kTlMaxWg), te(kTlMaxTiles);
+        std::vector<uint32_t> hw(2 * kTlMaxWg), tw(kTlMaxTiles);
+        RP_HIP(hipStreamSynchronize(st));
+        RP_HIP(hipMemcpyFromSymbol(wg.data(), HIP_SYMBOL(g_tl_wg), 8 * wg.size()));
+        RP_HIP(hipMemcpyFromSymbol(hw.data(), HIP_SYMBOL(g_tl_hw), 4 * hw.size()));
+        RP_HIP(hipMemcpyFromSymbol(te.data(), HIP_SYMBOL(g_tl_tile), 8 * te.size()));
+        RP_HIP(hipMemcpyFromSymbol(tw.data(), HIP_SYMBOL(g_tl_tile_wg), 4 * tw.size()));
+        if (FILE* f = fopen(k.tl_dump, "w")) {
+            fprintf(f, "# sort %d ticket %d grid %u stagger %d tiles %llu\n", sort_t, ticket ? 1 : 0, sg, stag16,
+                    (unsigned long long)stiles);
+            for (uint32_t i = 0; i < nwg; i++)
+                fprintf(f, "W %u %u %u %llu %llu\n", i, hw[2 * i], hw[2 * i + 1], wg[2 * i], wg[2 * i + 1]);
+            for (uint32_t i = 0; i < nt; i++) fprintf(f, "T %u %u %llu\n", i, tw[i], te[i]);
+            fclose(f);
+        }
+    }
+#endif
     // (t0 > 0: TK is 2048, the lists are uniform)
     lookupn_tiles_end(r, k, b, t0 + ntiles, TK, done, cv.ablate != 3 && !fuse, 0,
                       [&](auto keys_done, auto tot, auto over, const uint32_t*) {
-                          fprintf(stderr, "[rp] compact lookupN: %llu keys, %llu deferred, %llu overflowed tiles (cb %u ob %u fsh %u sort %d)\n",
-                                  keys_done, tot, over, r.ccb, r.cob, r.cfsh, sort_t);
+                          fprintf(stderr, "[rp] compact lookupN: %llu keys, %llu deferred, %llu overflowed tiles (cb %u ob %u fsh %u sort %d) "
+                                          "ticket %d grid %u stagger %d\n",
+                                  keys_done, tot, over, r.ccb, r.cob, r.cfsh, sort_t, ticket ? 1 : 0, sg, stag16);
                       });
 }
 

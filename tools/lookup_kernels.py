@@ -28,7 +28,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KNOBS = ("RP_RING_WIDE", "RP_RING_NOWINDOW", "RP_RING_LAYOUT", "RP_LOOKUP_ABLATE", "RP_LOOKUP_WPRED", "RP_LOOKUP_HINT",
          "RP_LOOKUP_LDS", "RP_LOOKUP_LDS_GRID", "RP_LOOKUP_LDS_STG", "RP_LOOKUP_LDS_ABL", "RP_LOOKUP_WS",
          "RP_LOOKUP_WS_GRID", "RP_LOOKUP_WS_ABL", "RP_LOOKUP_KPL", "RP_LOOKUP_SORT", "RP_LOOKUP_GRID", "RP_LOOKUP_LEAN",
-         "RP_LOOKUP_HALF", "RP_LOOKUP_FUSEFIX", "RP_LOOKUP_STG", "RP_LOOKUP_LH", "RP_LOOKUP_STGHS", "RP_LOOKUP_DEBUG")
+         "RP_LOOKUP_HALF", "RP_LOOKUP_FUSEFIX", "RP_LOOKUP_STG", "RP_LOOKUP_LH", "RP_LOOKUP_STGHS", "RP_LOOKUP_DEBUG",
+         "RP_LOOKUP_TICKET", "RP_LOOKUP_STAGGER", "RP_LOOKUP_TICKET_GRID")
 
 
 def literal(path, name):
@@ -43,6 +44,7 @@ def environments():
     envs = [("layout:" + k, v) for k, v in literal("tests/test_ring_gpu.py", "LAYOUTS").items()]
     envs += [("ab:" + k, v[0]) for k, v in literal("tools/ab_lookup.py", "variants").items()]
     envs += [("sort:" + s, {"RP_LOOKUP_SORT": s}) for s in ("0", "256", "512", "1024")]
+    envs += [("ticket:" + s, {"RP_LOOKUP_TICKET": s}) for s in ("0", "1")]
     return envs
 
 

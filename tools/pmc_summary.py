@@ -20,7 +20,8 @@ def main():
     for f in glob.glob(os.path.join(d, "*", "run_counter_collection.csv")):
         for r in csv.DictReader(open(f)):
             k = r["Kernel_Name"]
-            if "k_lookupn_sorted<256, 3" in k or "k_lookupn_sortedILi256ELi3E" in k:
+            if ("k_lookupn_sorted<256, 3" in k or "k_lookupn_sortedILi256ELi3E" in k
+                    or "k_lookupn_sorted_ticket<256, 3" in k or "k_lookupn_sorted_ticketILi256ELi3E" in k):
                 kk = "compact"
             elif "k_lookupn_probe<36, 2, 1>" in k:
                 kk = "hashonly"
