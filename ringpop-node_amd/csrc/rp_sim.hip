@@ -977,7 +977,8 @@ __device__ __forceinline__ int64_t wave_max64(int64_t v) {
 }
 
 // A lane's cursor over its listed deviated pieces (uint4 {base offset, member, blen | nl << 8 |
-// status << 16 | basedig << 18, rank}), in 32-bit lane coordinates: the current piece spans
+// status << 16 | basedig << 18 | plen << 19, rank}; blen, nl and plen at most 255, pass 1 sends a
+// view with a longer piece to the fallback), in 32-bit lane coordinates: the current piece spans
 // [pos, pend) at shift delta before it; nxt (the next entry) is loaded one piece ahead, so a
 // piece boundary costs no dependent memory round trip.
 struct LaneCursor {
@@ -1062,7 +1063,9 @@ __device__ void lane_pass1(const SimDev& S, const LaneView& V, uint4* dl, int64_
                 const uint32_t blen = (uint32_t)(S.boff[k + 1] - bpos);
                 const uint32_t nl = (uint32_t)(S.noff[a + 1] - S.noff[a]);
                 const uint32_t plen = (uint32_t)((int64_t)blen + d);
-                if (plen > 0xFFu) nd = S.dcap;  // a piece too long for the record: this lane falls back
+                // a piece too long for the record, in the base string or in this view (fewer digits
+                // make plen <= 255 < blen): this lane falls back
+                if ((plen | blen | nl) > 0xFFu) nd = S.dcap;
                 dl[nd < S.dcap ? nd : 0] =
                     uint4{bpos, a, blen | (nl << 8) | ((uint32_t)st << 16) | ((x == x0 ? 1u : 0u) << 18) | (plen << 19), k};
             }
@@ -1117,7 +1120,7 @@ __device__ void seg_pass1(const SimDev& S, const LaneView& V, uint4* dl, bool ac
                     const uint32_t blen = (uint32_t)(S.boff[k + 1] - bpos);
                     const uint32_t nl = (uint32_t)(S.noff[a + 1] - S.noff[a]);
                     const uint32_t plen = (uint32_t)((int64_t)blen + d);
-                    if (plen > 0xFFu) big = true;
+                    if ((plen | blen | nl) > 0xFFu) big = true;
                     dl[idx] = uint4{bpos, a, blen | (nl << 8) | ((uint32_t)st << 16) | ((x == x0 ? 1u : 0u) << 18) |
                                                  (plen << 19),
                                     k};
